@@ -11,6 +11,9 @@ workload c3 additionally one 512x512 view + question/answer ids per scene.  One 
 each rank owns its own B=16 batch (weak scaling), gradients are all-reduced over RCCL.
 Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` for the dominant
 kernel and `cpu_baseline` (the CPU oracle port timed on a bounded sample; N=1 only).
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy; that step starts from the seeded
+initial weights and a fresh optimizer (restored off the clock), so its inputs are the same in every run and two builds run
+with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -34,6 +37,8 @@ WORKLOADS = {
 WORKLOADS["c5"] = ("c5 (one rank's share): " + WORKLOADS["c3"][4:] + " -- at B=32 x 80000 points + one 1024x1024 view "
                    "(4097 image tokens) per scene")
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: elements kept per array (16 MB in float32)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all arrays together
 
 
 def parse():
@@ -86,7 +91,13 @@ def parse():
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16",
                     help="arithmetic of the dense layers: bf16 = the HIP kernel path (MFMA GEMMs, point-major detector); "
                          "f32 = the reference composition on torch ops (c2 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss, the parameters the "
+                         "optimizer left, their gradients, the floating-point buffers) as DIR/<name>.npy, %d MB at most"
+                         % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     big = args.workload == "c5"
     args.batch = args.batch or (32 if big else 16)
     args.points = args.points or (80000 if big else 40000)
@@ -237,6 +248,76 @@ class OpTimer(object):
         for n, shape, s, e in self.records:
             agg.setdefault((n, shape), []).append(s.elapsed_time(e))
         return {k: (sorted(v)[len(v) // 2], len(v)) for k, v in agg.items()}
+
+
+def _flat_sample(tensors, seed):
+    """`tensors` (None = a zero tensor of `numel` elements) flattened and concatenated in order, as float32 on the host: every
+    element when there are at most DUMP_SAMPLE, else DUMP_SAMPLE of them at sorted positions drawn from a generator seeded
+    with `seed` -- the same positions in every run with the same arguments.  Items are (tensor or None, numel)."""
+    import numpy as np
+    total = sum(n for _, n in tensors)
+    pos = None
+    if total > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        pos = torch.randint(0, total, (DUMP_SAMPLE,), generator=g).sort().values
+    out, off = [], 0
+    for t, n in tensors:
+        if pos is None:
+            lo, hi, take = 0, n, None
+        else:
+            lo, hi = torch.searchsorted(pos, torch.tensor([off, off + n])).tolist()
+            take = pos[lo:hi] - off
+        if hi > lo:
+            if t is None:
+                out.append(torch.zeros(hi - lo))
+            else:
+                flat = t.detach().reshape(-1)
+                out.append((flat if take is None else flat[take.to(flat.device)]).float().cpu())
+        off += n
+    return torch.cat(out).numpy() if out else np.zeros(0, np.float32)
+
+
+def initial_state(model):
+    return {k: v.detach().clone() for k, v in model.state_dict().items()}
+
+
+def restore_initial_state(model, opt, state):
+    """--dump-outputs, before the last timed step (off the clock): parameters and buffers back to the seeded values the run
+    started from and the optimizer back to fresh (zero moments and step count), in place, so that the captured graphs keep
+    their operands.  The steps before it sum some gradients with fp32 atomics, and this loss turns rounding-level
+    differences into different trajectories; from the same state the step itself reproduces to rounding.  With this the
+    dumped step has the same inputs in every run.  (As PhasedTrainStep.capture puts back the state of its warm-up steps.)"""
+    from bridgeqa_amd import fusion_ops
+    with torch.no_grad():
+        for k, v in model.state_dict().items():
+            v.copy_(state[k])
+        for st in opt.state.values():
+            for t in st.values():
+                if torch.is_tensor(t):
+                    t.zero_()
+    fusion_ops.refresh_shadows(only_with_grad=False)   # the bf16 operand copies of the restored weights
+    fusion_ops.mark_transposed_stale()
+    torch.cuda.synchronize()
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the parameters the optimizer left, their
+    gradients (zero where a parameter received none) and the floating-point buffers (BatchNorm running statistics) -- as
+    path/<name>.npy.  Called right after the timed steps, before anything else runs on the model."""
+    import numpy as np
+    if torch.cuda.is_initialized():
+        torch.cuda.synchronize()
+    params = [p for _, p in model.named_parameters()]
+    arrays = {
+        "loss": np.asarray([loss.detach().double().item()], np.float64),
+        "parameters": _flat_sample([(p, p.numel()) for p in params], 1),
+        "gradients": _flat_sample([(p.grad, p.numel()) for p in params], 1),   # (same seed: the same positions)
+        "buffers": _flat_sample([(b, b.numel()) for _, b in model.named_buffers() if b.is_floating_point()], 2),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def make_batch(args, workload, B, seed, device):
@@ -506,7 +587,7 @@ class _StaticLoader(object):
             yield dict(self.batch)
 
 
-def run_reference_loop(args, model, batch, dev, use_graph, steps, warmup, trace=False):
+def run_reference_loop(args, model, batch, dev, use_graph, steps, warmup, trace=False, dump_dir=None):
     """The reference's training iteration as its solver writes it (lib/solver.py:463-595 _feed / _forward / _backward,
     scripts/train.py:410-417), the loop BODY unchanged: forward through the module API, the loss outside the model,
     zero_grad / backward / (clip inside) optimizer.step.  With graphs: graphed.enable(model, optimizer) replays HIP graphs
@@ -515,6 +596,7 @@ def run_reference_loop(args, model, batch, dev, use_graph, steps, warmup, trace=
     -> dict for the JSON line"""
     from bridgeqa_amd import graphed
     from bridgeqa_amd.optim import FusedAdamW
+    state0 = initial_state(model) if dump_dir else None
     opt = FusedAdamW(model.parameters(), lr=5e-4, weight_decay=1e-5, grad_clip_value=1.0)
     loss_fn = total_loss
     prefetch = use_graph and not getattr(args, "no_prefetch", False)
@@ -550,12 +632,20 @@ def run_reference_loop(args, model, batch, dev, use_graph, steps, warmup, trace=
     t0 = time.perf_counter()
     host = []
     h0 = time.perf_counter()
-    for data_dict in loader(steps):
+    for i, data_dict in enumerate(loader(steps)):
+        if state0 is not None and i == steps - 1:   # (see restore_initial_state; not timed, the steps before it are)
+            torch.cuda.synchronize()
+            r0 = time.perf_counter()
+            restore_initial_state(model, opt, state0)
+            t0 += time.perf_counter() - r0
+            h0 += time.perf_counter() - r0
         loss = body(data_dict)
         host.append((time.perf_counter() - h0) * 1e3)
         h0 = time.perf_counter()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(dump_dir, model, loss)
     assert torch.isfinite(loss).item()
     print("reference loop, host-side time per step: %.2f ms  (%s)" % (sum(host) / len(host), "  ".join("%s %.2f" % (k, v / steps) for k, v in seg.items())),
           file=sys.stderr)
@@ -585,7 +675,7 @@ def run_reference_loop(args, model, batch, dev, use_graph, steps, warmup, trace=
 def reference_loop(args, model, batch, dev, use_graph):
     """`--loop reference`: ONLY the drop-in loop, as its own JSON line"""
     res = run_reference_loop(args, model, batch, dev, use_graph, args.steps, args.warmup,
-                             trace=os.environ.get("BQ_PIPE_TRACE") == "1")
+                             trace=os.environ.get("BQ_PIPE_TRACE") == "1", dump_dir=args.dump_outputs)
     out = {"metric": "train samples/s (%dk-pt scene + %d^2 view, bs%d)" % (args.points // 1000, args.image, args.batch),
            "value": res["samples_per_s"], "unit": "samples/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "weak",
@@ -750,6 +840,7 @@ def main():
         fusion_ops.set_compute_dtype(torch.bfloat16)
     torch.manual_seed(0)
     model = build_model(workload, args.cin, args.image).to(dev)
+    state0 = initial_state(model) if args.dump_outputs else None
     dp = world > 1 or args.dp_path  # data-parallel structure: graph(fwd+bwd) -> flat bf16 all-reduce -> fused AdamW
     use_graph = args.graph in ("on", "auto")
     batch = make_batch(args, workload, args.batch, 42 + rank, dev)
@@ -962,7 +1053,12 @@ def main():
     t0 = time.perf_counter()
     host_ms = 0.0
     host_each = []
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if state0 is not None and i == args.steps - 1:
+            torch.cuda.synchronize()   # (the steps before it stay on the clock; the restore itself is not timed)
+            r0 = time.perf_counter()
+            restore_initial_state(model, opt, state0)
+            t0 += time.perf_counter() - r0
         h0 = time.perf_counter()
         loss = step()
         host_each.append((time.perf_counter() - h0) * 1e3)
@@ -971,6 +1067,8 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)   # (before the eager re-run below, which steps the optimizer again)
     if graphed:
         # a replayed graph runs no Python, so the per-kernel HIP events are taken on an eager re-run of the same
         # step (same kernels, same stream) right after the timed region; it is not part of `value`

@@ -40,3 +40,35 @@ def test_two_ranks_sharing_one_device_stay_in_sync(workload, extra):
         assert comm["exposed_ms"] is not None and comm["exposed_ms"] >= 0
         want = "reduce_scatter" if "reduce_scatter" in extra else "all_reduce"
         assert all(g["algo"] == want for g in comm["groups"].values())
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs on one GPU, the phased c3 step at a small size, twice: the JSON line reports the --steps asked for, DIR
+    holds the last timed step's loss, parameters, gradients and buffers as finite float32 / float64 arrays (64 MB at most),
+    and the two runs agree to rounding (the dumped step starts from the seeded state: bench.restore_initial_state)"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c3", "--batch", "2",
+                            "--points", "4096", "--image", "128", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                            "--no-loop-reference", "--dump-outputs", str(out_dir)],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 3, r.stdout[-2000:]
+        dumps.append({f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)})
+    a, b = dumps
+    assert set(a) == {"loss", "parameters", "gradients", "buffers"}
+    assert all(x.dtype in (np.float32, np.float64) and x.size > 0 and np.isfinite(x).all() for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert np.abs(a["gradients"]).max() > 0
+    # measured: loss and buffers bit-identical, gradients within 3e-10 of their largest element, parameters within 1 ulp
+    # (what is left are fp32 atomic sums)
+    for n in a:
+        x, y = a[n].astype(np.float64), b[n].astype(np.float64)
+        assert x.shape == y.shape, n
+        tol = 1e-6 * np.abs(x).max() + 1e-4 * np.abs(x)
+        assert (np.abs(x - y) <= tol).all(), (n, float(np.abs(x - y).max()))
