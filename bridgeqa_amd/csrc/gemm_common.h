@@ -245,11 +245,15 @@ __device__ __forceinline__ void lds_dma16(i32x4_rs rs, const void *lds, unsigned
 }
 
 // the closed-form contraction-major read (read_frag_cf<true>) as inline asm, for the same reason as read_frag_asm; the
-// K-contiguous form stays a compiler-visible load (hipcc does not fence those: tools/isa_waits.py)
+// K-contiguous form stays a compiler-visible load (hipcc does not fence those: tools/isa_waits.py).
+// BQ_CF_ASM_READS=0 (measurement / test builds, tests/test_lds_pipeline_gpu.py) restores the compiler-visible read.
+#ifndef BQ_CF_ASM_READS
+#define BQ_CF_ASM_READS 1
+#endif
 template <bool XC>
 __device__ __forceinline__ bf16x8 read_frag_cf_x(const unsigned char *unit, int sub16, int kk, int kc_base, int xc0, int xcg) {
-  if (!XC) {
-    return read_frag_cf<false>(unit, sub16, kk, kc_base, xc0, xcg);
+  if (!XC || !BQ_CF_ASM_READS) {
+    return read_frag_cf<XC>(unit, sub16, kk, kc_base, xc0, xcg);
   } else {
     bf16x4 lo, hi;
     const unsigned a = lds_addr_of(unit) + (unsigned)(xc0 + ((sub16 ^ xcg) << 5) + kk * 4096);

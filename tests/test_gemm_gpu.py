@@ -317,12 +317,22 @@ def test_repeatable_under_load(dev):
     dw0 = _ext.gemm_dw(dy, x, tile=256)
     _check(dw0, dy.float().t() @ x.float(), f32=True)
     junk = torch.empty(1 << 28, device=dev, dtype=torch.uint8)
-    for it in range(12):
-        if it % 3 == 0:
-            junk.fill_(it)  # evict L2 / Infinity Cache
-        assert torch.equal(_ext.gemm_fwd(x, w, None, tile=256), y0), it
-        assert torch.equal(_ext.gemm_dx(dy, w, tile=256), dx0), it
-        assert torch.equal(_ext.gemm_dw(dy, x, tile=256), dw0), it
+    side = torch.cuda.Stream()
+    big = torch.zeros(256 << 20, device=dev, dtype=torch.uint8)
+    side.wait_stream(torch.cuda.current_stream())
+    big.record_stream(side)
+    try:
+        for it in range(12):
+            if it % 3 == 0:
+                junk.fill_(it)  # evict L2 / Infinity Cache
+            with torch.cuda.stream(side):
+                for _ in range(4):
+                    big.add_(1)     # HBM-bound traffic beside the GEMMs
+            assert torch.equal(_ext.gemm_fwd(x, w, None, tile=256), y0), it
+            assert torch.equal(_ext.gemm_dx(dy, w, tile=256), dx0), it
+            assert torch.equal(_ext.gemm_dw(dy, x, tile=256), dw0), it
+    finally:
+        torch.cuda.synchronize()   # (no side-stream write outlives the test, also when an assert ends it)
 
 
 def test_rejects_bad_arguments(dev):
