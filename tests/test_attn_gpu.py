@@ -6,6 +6,8 @@ import math
 import pytest
 import torch
 
+from attn_ref import _keep_mask
+
 pytestmark = pytest.mark.gpu
 
 
@@ -239,17 +241,6 @@ def test_stream_overlap_is_value_neutral(dev):
                 assert torch.equal(a, b)
     finally:
         fusion_ops.set_compute_dtype(prev_dt)
-
-
-def _keep_mask(seed, B, H, Lq, Lk, p, dev):
-    """The kernel's stateless dropout hash (csrc/attn.hip drop_keep), restated with 64-bit integer tensors."""
-    M = 0xFFFFFFFF
-    bh = torch.arange(B * H, device=dev, dtype=torch.int64).view(B, H, 1, 1)
-    q = torch.arange(Lq, device=dev, dtype=torch.int64).view(1, 1, Lq, 1)
-    k = torch.arange(Lk, device=dev, dtype=torch.int64).view(1, 1, 1, Lk)
-    x = (seed & M) ^ ((bh * 0x9E3779B1) & M) ^ ((q * 0x85EBCA77) & M) ^ ((k * 0xC2B2AE3D) & M)
-    x = x ^ (x >> 16); x = (x * 0x7feb352d) & M; x = x ^ (x >> 15); x = (x * 0x846ca68b) & M; x = x ^ (x >> 16)
-    return x >= int(p * 4294967296.0)
 
 
 @pytest.mark.parametrize("B,H,Lq,Lk,p", [(2, 3, 20, 1045, 0.0), (2, 12, 20, 276, 0.1), (3, 2, 5, 20, 0.1),

@@ -23,6 +23,8 @@ import sys
 import pytest
 import torch
 
+from load_util import _repeat_under_load
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -369,29 +371,6 @@ def test_default_build_equals_the_compiler_fenced_build_bit_for_bit(fenced_lib, 
 
 
 # ---- repeatability under load ---------------------------------------------------------------------------------------------
-def _repeat_under_load(dev, fns):
-    """every fn() 12 times, bit-identical to its first result, with a side stream adding to 256 MB and the L2 evicted every
-    third iteration"""
-    first = [tuple(t.clone() for t in f()) for f in fns]
-    side = torch.cuda.Stream()
-    big = torch.zeros(256 << 20, device=dev, dtype=torch.uint8)
-    junk = torch.empty(1 << 28, device=dev, dtype=torch.uint8)
-    side.wait_stream(torch.cuda.current_stream())
-    big.record_stream(side)
-    try:
-        for it in range(12):
-            if it % 3 == 0:
-                junk.fill_(it)  # evict L2 / Infinity Cache
-            with torch.cuda.stream(side):
-                for _ in range(4):
-                    big.add_(1)   # HBM-bound traffic beside the kernels
-            for k, f in enumerate(fns):
-                for a, b in zip(f(), first[k]):
-                    assert torch.equal(a, b), (k, it)
-    finally:
-        torch.cuda.synchronize()   # (no side-stream write outlives the test, also when an assert ends it)
-
-
 def test_contraction_major_gemm_repeatable_under_load(dev):
     from bridgeqa_amd import _ext
     dy, x = _rand((16400, 768), dev, 700), _rand((16400, 768), dev, 701)
