@@ -1565,3 +1565,87 @@ def three_interpolate_grad_gather(grad_out, inv, weight, m):
         _check(_lib.bq_three_interpolate_grad_gather(_p(grad_out), _p(inv[0]), _p(inv[1]), _p(weight), _p(out), B, C, n, int(m),
                                                      _stream()), "three_interpolate_grad_gather")
     return out
+
+
+# ---- eval-mode SharedMLP of one detector module in one launch (csrc/mlp_eval.hip) ----------------------------------------
+class _MlpEvalLayer(ctypes.Structure):
+    _fields_ = [("w", _vp), ("gamma", _vp), ("beta", _vp), ("mean", _vp), ("var", _vp), ("bias", _vp), ("eps", _f),
+                ("n", _i), ("ldw", _i), ("relu", _i)]
+
+
+class _MlpEvalDesc(ctypes.Structure):
+    _fields_ = [("xyz", _vp), ("new_xyz", _vp), ("feats", _vp), ("f_bs", _l), ("f_rs", _l), ("idx", _vp),
+                ("B", _i), ("C", _i), ("N", _i), ("M", _i), ("S", _i), ("radius", _f), ("normalize", _i),
+                ("x", _vp), ("ldx", _l), ("K", _i), ("R", _l), ("n_layers", _i), ("layers", _MlpEvalLayer * 3),
+                ("has_tail", _i), ("tail", _MlpEvalLayer), ("out", _vp), ("pool", _i)]
+
+
+_lib.bq_mlp_eval.argtypes = [ctypes.POINTER(_MlpEvalDesc), _vp]
+_lib.bq_mlp_eval.restype = ctypes.c_int
+MLP_EVAL_KMAX = 512     # input channels (rounded up to 32) the kernel stages
+MLP_EVAL_S = (16, 32, 64)
+
+
+def mlp_eval_width_ok(n):
+    """a BatchNorm layer width the fused eval kernel covers"""
+    return n % 32 == 0 and 32 <= n <= 256
+
+
+def _mlp_eval_layer(dst, spec):
+    """spec: dict(w=(n, ldw) bf16 rows, zero beyond the input width; mean, var, eps; optional gamma, beta, bias; relu)"""
+    w = spec["w"]
+    if w.dtype != torch.bfloat16 or w.dim() != 2 or w.stride(1) != 1:
+        raise RuntimeError("mlp_eval: weights must be bf16 (n, ldw) rows")
+    for k in ("gamma", "beta", "mean", "var", "bias"):
+        t = spec.get(k)
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != w.device):
+            raise RuntimeError("mlp_eval: %s must be a contiguous float tensor on the weights' device" % k)
+    dst.w, dst.n, dst.ldw = w.data_ptr(), w.shape[0], w.stride(0)
+    for k in ("gamma", "beta", "mean", "var", "bias"):
+        setattr(dst, k, _p(spec.get(k)))
+    dst.eps, dst.relu = float(spec.get("eps", 0.0)), int(bool(spec.get("relu", True)))
+
+
+def mlp_eval(layers, tail=None, grouped=None, rows=None, pool=False):
+    """One eval-mode detector module in one launch.  grouped = (xyz, new_xyz, feats_pm | None, idx, radius, normalize) -- the
+    operands of group_concat_pm -- or rows = (x (R, >= K) bf16 rows with contiguous channels, K).  layers: 1..3 BatchNorm
+    layer specs (see _mlp_eval_layer), tail: a last linear spec (w, bias) with fp32 output.  Returns bf16 (B M, n) maxima
+    (pool), fp32 (R, n_tail) (tail) or bf16 (R, n) rows."""
+    d = _MlpEvalDesc()
+    if grouped is not None:
+        xyz, new_xyz, feats, idx, radius, normalize = grouped
+        _req(xyz, torch.float32, "xyz"); _req(new_xyz, torch.float32, "new_xyz"); _req(idx, torch.int32, "idx")
+        B, N, _ = xyz.shape
+        _, M, S = idx.shape
+        d.xyz, d.new_xyz, d.idx = xyz.data_ptr(), new_xyz.data_ptr(), idx.data_ptr()
+        d.B, d.N, d.M, d.S, d.radius, d.normalize = B, N, M, S, float(radius), int(bool(normalize))
+        if feats is not None:
+            if not feats.is_cuda or feats.dtype != torch.float32 or feats.stride(2) != 1:
+                raise RuntimeError("feats_pm must be a CUDA float tensor (B,N,C) with contiguous rows")
+            d.feats, d.C, d.f_bs, d.f_rs = feats.data_ptr(), feats.shape[2], feats.stride(0), feats.stride(1)
+        d.R = B * M * S
+        dev, R = xyz.device, B * M * S
+    else:
+        x, K = rows
+        if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+            raise RuntimeError("mlp_eval: rows must be a CUDA bf16 (R, ld) tensor with contiguous channels")
+        d.x, d.ldx, d.K, d.R = x.data_ptr(), x.stride(0), int(K), x.shape[0]
+        dev, R = x.device, x.shape[0]
+    d.n_layers = len(layers)
+    if not 1 <= len(layers) <= 3:
+        raise RuntimeError("mlp_eval: %d layers (1..3)" % len(layers))
+    for i, spec in enumerate(layers):
+        _mlp_eval_layer(d.layers[i], spec)
+    n = layers[-1]["w"].shape[0]
+    with torch.cuda.device(dev):
+        if tail is not None:
+            d.has_tail = 1
+            _mlp_eval_layer(d.tail, dict(tail, relu=False))
+            out = torch.empty(R, tail["w"].shape[0], dtype=torch.float32, device=dev)
+        elif pool:
+            out = torch.empty(R // d.S, n, dtype=torch.bfloat16, device=dev)
+        else:
+            out = torch.empty(R, n, dtype=torch.bfloat16, device=dev)
+        d.out, d.pool = out.data_ptr(), int(bool(pool))
+        _check(_lib.bq_mlp_eval(ctypes.byref(d), _stream()), "mlp_eval")
+    return out

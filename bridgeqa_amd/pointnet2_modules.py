@@ -67,6 +67,14 @@ class PointnetSAModuleVotes(nn.Module):
                 assert inds.shape[1] == self.npoint
             new_xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), inds) \
                 .transpose(1, 2).contiguous()
+        if self._eval_native_ok(xyz, features):
+            # eval-mode BatchNorm: grouping, the whole SharedMLP and the max over nsample in ONE launch
+            # (csrc/mlp_eval.hip); the grouped tensor and the intermediate activations never reach HBM
+            if group_idx is None:
+                group_idx = pointnet2_utils.ball_query(self.grouper.radius, self.grouper.nsample, xyz, new_xyz)
+            new_features = pt_utils.native_eval(self._eval_run, self._eval_compose, (xyz, new_xyz, features, group_idx),
+                                                list(self.mlp_module.parameters()))
+            return new_xyz, new_features, inds
         grouped_features, _grouped_xyz = self.grouper(xyz, new_xyz, features, idx=group_idx, inv=inv)  # (B, 3+C, npoint, nsample)
         # max over nsample == F.max_pool2d(kernel=[1, nsample]).squeeze(-1) (pointnet2_modules.py:259-262, 272); a row
         # reduction instead of the generic NCHW pooling kernel.  Tie routing in backward is immaterial.
@@ -81,6 +89,31 @@ class PointnetSAModuleVotes(nn.Module):
             new_features = self.mlp_module(grouped_features)
             new_features = new_features.max(dim=3)[0].float()  # module boundary stays fp32 (reference dtype)
         return new_xyz, new_features, inds
+
+    def _eval_native_ok(self, xyz, features):
+        """the fused eval kernel's preconditions (checked for every layer before any runs)"""
+        from . import _ext
+        C = 0 if features is None else features.shape[1]
+        return (pt_utils.native_rows_ok(xyz) and self.use_xyz and self.nsample in _ext.MLP_EVAL_S
+                and xyz.dtype == torch.float32 and xyz.is_contiguous()
+                and (features is None or (features.dtype == torch.float32 and features.is_cuda))
+                and (3 + C + 31) // 32 * 32 <= _ext.MLP_EVAL_KMAX and self.mlp_module[0].conv.in_channels == 3 + C
+                and pt_utils.eval_mlp_ok(self.mlp_module))
+
+    def _eval_run(self, xyz, new_xyz, features, idx):
+        from . import _ext
+        out = _ext.mlp_eval(pt_utils.eval_mlp_specs(self.mlp_module), pool=True,
+                            grouped=(xyz, new_xyz.contiguous(), pointnet2_utils.point_major(features), idx,
+                                     self.grouper.radius, self.normalize_xyz))
+        B, M = idx.shape[0], idx.shape[1]
+        return out.view(B, M, -1).float().transpose(1, 2)
+
+    def _eval_compose(self, xyz, new_xyz, features, idx):
+        """the eval-mode composition: grouping + SharedMLP (+ max over nsample) as forward runs them without the kernel"""
+        grouped_features, _ = self.grouper(xyz, new_xyz, features, idx=idx)
+        if grouped_features.dtype == torch.bfloat16:
+            return self.mlp_module(grouped_features, pool=True).float().transpose(1, 2)
+        return self.mlp_module(grouped_features).max(dim=3)[0].float()
 
 
 class PointnetFPModule(nn.Module):
@@ -107,6 +140,9 @@ class PointnetFPModule(nn.Module):
             new_features = torch.cat([interpolated_feats, unknow_feats], dim=1)
         else:
             new_features = interpolated_feats
+        if self._eval_native_ok(new_features):
+            # eval-mode BatchNorm: the whole SharedMLP in ONE launch (csrc/mlp_eval.hip)
+            return pt_utils.native_eval(self._eval_run, self._eval_compose, (new_features,), list(self.mlp.parameters()))
         if (pt_utils.native_rows_ok(new_features) and self.training
                 and all(pt_utils._native_layer_ok(layer) for layer in self.mlp) and new_features.shape[1] % 8 == 0):
             # point-major bf16 rows through the native SharedMLP layers (GEMM + BatchNorm statistics in its epilogue);
@@ -116,3 +152,19 @@ class PointnetFPModule(nn.Module):
             out = self.mlp(rows.view(B, n, 1, C).permute(0, 3, 1, 2))
             return out.squeeze(-1).float()
         return self.mlp(new_features.unsqueeze(-1)).squeeze(-1)
+
+    def _eval_native_ok(self, x):
+        from . import _ext
+        return (pt_utils.native_rows_ok(x) and x.dim() == 3 and x.shape[1] % 8 == 0 and x.dtype == torch.float32
+                and (x.shape[1] + 31) // 32 * 32 <= _ext.MLP_EVAL_KMAX and self.mlp[0].conv.in_channels == x.shape[1]
+                and pt_utils.eval_mlp_ok(self.mlp))
+
+    def _eval_run(self, x):
+        from . import _ext
+        B, C, n = x.shape
+        out = _ext.mlp_eval(pt_utils.eval_mlp_specs(self.mlp), rows=(pt_utils.to_rows(x), C))
+        res = torch.empty(B, out.shape[1], n, dtype=torch.float32, device=x.device)
+        return res.copy_(out.view(B, n, -1).transpose(1, 2))   # the fp32 (B, C, n) layout of the eval composition
+
+    def _eval_compose(self, x):
+        return self.mlp(x.unsqueeze(-1)).squeeze(-1)

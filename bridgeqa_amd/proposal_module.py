@@ -74,6 +74,10 @@ class ProposalModule(nn.Module):
         + ReLU stages run as native point-major layers and the last convolution as a linear on the rows"""
         from . import pytorch_utils as pt_utils
         p = self.proposal
+        if self._eval_native_ok(features):
+            # eval-mode BatchNorm: both conv + BatchNorm + ReLU stages and the last convolution in ONE launch
+            # (csrc/mlp_eval.hip)
+            return pt_utils.native_eval(self._eval_run, p, (features,), list(p.parameters()))
         if (pt_utils.native_rows_ok(features) and self.training and features.shape[1] % 8 == 0
                 and pt_utils.rows_layer_ok(p[0], p[1]) and pt_utils.rows_layer_ok(p[3], p[4])):
             # (both layers' preconditions are checked before either runs: no fallback after a BatchNorm update)
@@ -83,6 +87,27 @@ class ProposalModule(nn.Module):
             net = pt_utils.rows_linear_f32(h, p[6].weight.squeeze(-1), p[6].bias)
             return net.view(B, K, -1).transpose(1, 2)
         return p(features)
+
+    def _eval_native_ok(self, x):
+        from . import _ext
+        from . import pytorch_utils as pt_utils
+        p = self.proposal
+        last = p[6]
+        return (pt_utils.native_rows_ok(x) and x.dim() == 3 and x.shape[1] % 8 == 0 and x.dtype == torch.float32
+                and (x.shape[1] + 31) // 32 * 32 <= _ext.MLP_EVAL_KMAX and p[0].in_channels == x.shape[1]
+                and pt_utils.eval_layer_ok(p[0], p[1]) and pt_utils.eval_layer_ok(p[3], p[4])
+                and isinstance(p[2], nn.ReLU) and isinstance(p[5], nn.ReLU)
+                and last.weight.dtype == torch.float32 and last.kernel_size == (1,) and last.groups == 1
+                and last.stride == (1,) and last.padding == (0,) and last.dilation == (1,))
+
+    def _eval_run(self, x):
+        from . import _ext
+        from . import pytorch_utils as pt_utils
+        p = self.proposal
+        B, C, K = x.shape
+        net = _ext.mlp_eval([pt_utils.eval_layer_spec(p[0], p[1]), pt_utils.eval_layer_spec(p[3], p[4])],
+                            tail=pt_utils.eval_tail_spec(p[6]), rows=(pt_utils.to_rows(x), C))
+        return net.view(B, K, -1).transpose(1, 2)
 
     def forward(self, xyz, features, data_dict):
         """xyz (B,K,3) votes, features (B,C,K) -> data_dict with the proposal outputs."""

@@ -376,6 +376,83 @@ def native_rows_ok(x):
             and pointnet2_utils.backend_is_hip())
 
 
+def eval_layer_ok(conv, bn):
+    """conv1x1 (+ bias) -> BatchNorm in EVAL mode (running statistics) as the fused eval kernel covers it
+    (csrc/mlp_eval.hip): fp32 parameters and buffers, an output width that is a multiple of 32 up to 256"""
+    from . import _ext
+    return (bn is not None and not bn.training and bn.track_running_stats and bn.running_mean is not None
+            and bn.running_var is not None and bn.running_mean.dtype == torch.float32
+            and bn.running_var.dtype == torch.float32 and bn.num_features == conv.out_channels
+            and all(t is None or t.dtype == torch.float32 for t in (bn.weight, bn.bias, conv.bias))
+            and conv.weight.dtype == torch.float32 and conv.groups == 1 and all(k == 1 for k in conv.kernel_size)
+            and all(k == 1 for k in conv.stride) and all(k == 0 for k in conv.padding)
+            and all(k == 1 for k in conv.dilation) and _ext.mlp_eval_width_ok(conv.out_channels))
+
+
+def eval_mlp_ok(mlp):
+    """every layer of a SharedMLP is conv -> eval BatchNorm -> ReLU (or no activation) the fused eval kernel covers"""
+    layers = list(mlp)
+    return (1 <= len(layers) <= 3 and all(hasattr(l, "bn") and eval_layer_ok(l.conv, l.bn.bn) for l in layers)
+            and all(getattr(l, "activation", None) is None or isinstance(l.activation, nn.ReLU) for l in layers))
+
+
+def eval_layer_spec(conv, bn, relu=True):
+    """the bq_mlp_eval layer of conv -> eval BatchNorm (-> ReLU): the bf16 weight shadow and the LIVE BatchNorm tensors (the
+    kernel folds them at every launch)"""
+    from . import fusion_ops
+    return dict(w=fusion_ops.padded_conv_shadow(conv.weight), gamma=bn.weight, beta=bn.bias, mean=bn.running_mean,
+                var=bn.running_var, eps=bn.eps, bias=conv.bias, relu=relu)
+
+
+def eval_mlp_specs(mlp):
+    return [eval_layer_spec(l.conv, l.bn.bn, hasattr(l, "activation")) for l in mlp]
+
+
+def eval_tail_spec(conv):
+    from . import fusion_ops
+    return dict(w=fusion_ops.padded_conv_shadow(conv.weight), bias=conv.bias)
+
+
+class _NativeEval(torch.autograd.Function):
+    """A detector module in eval mode on the fused kernel (csrc/mlp_eval.hip), differentiable: the forward runs
+    `run(*inputs)` and saves only its inputs; the backward recomputes the module through its eval-mode composition
+    `compose(*inputs)` (the route the module takes without the kernel) under enable_grad and differentiates that.  args =
+    the n_in inputs, then the module's parameters (so that autograd routes their gradients here)."""
+
+    @staticmethod
+    def forward(ctx, run, compose, n_in, *args):
+        from . import fusion_ops
+        ctx.compose, ctx.n_in, ctx.params = compose, n_in, args[n_in:]
+        ctx.dtype = fusion_ops.compute_dtype()   # the composition is the one of the forward's compute dtype
+        ctx.save_for_backward(*args[:n_in])
+        return run(*args[:n_in])
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import fusion_ops
+        ins = ctx.saved_tensors
+        need = ctx.needs_input_grad[3:]
+        prev = fusion_ops.set_compute_dtype(ctx.dtype)
+        try:
+            with torch.enable_grad():
+                xs = [None if t is None else t.detach().requires_grad_(bool(need[i]) and t.is_floating_point())
+                      for i, t in enumerate(ins)]
+                out = ctx.compose(*xs)
+                wrt = [x for i, x in enumerate(xs) if x is not None and x.requires_grad]
+                wrt += [p for j, p in enumerate(ctx.params) if need[ctx.n_in + j]]
+                gs = list(torch.autograd.grad(out, wrt, g, allow_unused=True)) if wrt else []
+        finally:
+            fusion_ops.set_compute_dtype(prev)
+        res = [gs.pop(0) if (x is not None and x.requires_grad) else None for x in xs]
+        res += [gs.pop(0) if need[ctx.n_in + j] else None for j in range(len(ctx.params))]
+        return (None, None, None) + tuple(res)
+
+
+def native_eval(run, compose, inputs, params):
+    """run(*inputs) on the fused eval kernel; gradients (if any are wanted) from compose(*inputs), see _NativeEval"""
+    return _NativeEval.apply(run, compose, len(inputs), *inputs, *params)
+
+
 def _native_layer_ok(layer):
     """the native SharedMLP layer covers: conv without bias, training-mode BatchNorm2d with momentum and affine
     parameters, ReLU or no activation, output channels a multiple of 64 and a power of two (the BN kernels)"""

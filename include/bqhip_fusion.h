@@ -514,6 +514,47 @@ typedef struct bq_det_loss_seg {
 } bq_det_loss_seg;
 BQ_API int bq_det_loss_bwd(const bq_det_loss_seg *segments, int n, const float *upstream, void *stream);
 
+/* ---- eval-mode SharedMLP of one detector module in one launch (csrc/mlp_eval.hip) -----------------------------------
+ * Replaces, with every BatchNorm in eval mode, the conv1x1 -> BatchNorm -> ReLU stacks of
+ *   lib/pointnet2/pointnet2_modules.py:253-262 (PointnetSAModuleVotes: grouping, SharedMLP, max over nsample),
+ *   :330-340 (PointnetFPModule's SharedMLP), models/voting_module.py:33-40, models/proposal_module.py:44-50.
+ * Input, one of two forms:
+ *   grouped (xyz != NULL): the operands of bq_group_concat_pm -- xyz (B,N,3), new_xyz (B,M,3) f32, point-major f32 features
+ *     by batch / row strides f_bs / f_rs (feats NULL when C == 0), idx (B,M,S) int32, radius, normalize; row (b, j, k) is
+ *     the bf16 row bq_group_concat_pm writes (S in {16, 32, 64}; R = B M S);
+ *   rows (x != NULL): bf16 rows (R, ldx), K channels (K % 8 == 0, ldx % 8 == 0, 16-byte aligned).
+ * Layers (1..3): y = relu?(acc s + t), s = gamma / sqrt(running_var + eps), t = beta + (bias - running_mean) s, computed in
+ * the kernel from the pointers given (gamma / beta / bias NULL: 1 / 0 / 0); w bf16 (n, ldw) rows of the convolution weight,
+ * ldw >= the layer's input width rounded up to 32, zero in the padding; n a multiple of 32 up to 256.  The input width
+ * rounded up to 32 is at most 512.  Intermediate activations are rounded to bf16 and stay on chip.
+ * Output: pool (grouped form only): the max over each run of S rows, bf16 (B M, n_last) rows; has_tail: out = acc + bias of
+ * the tail layer (any width n, no BatchNorm), f32 (R, n); otherwise bf16 (R, n_last) rows.  Forward only. */
+typedef struct bq_mlp_eval_layer {
+  const void *w;
+  const float *gamma, *beta, *mean, *var, *bias;
+  float eps;
+  int n, ldw, relu;
+} bq_mlp_eval_layer;
+typedef struct bq_mlp_eval_desc {
+  const float *xyz, *new_xyz, *feats;
+  long f_bs, f_rs;
+  const int32_t *idx;
+  int B, C, N, M, S;
+  float radius;
+  int normalize;
+  const void *x;
+  long ldx;
+  int K;
+  long R;
+  int n_layers;
+  bq_mlp_eval_layer layers[3];
+  int has_tail;
+  bq_mlp_eval_layer tail;
+  void *out;
+  int pool;
+} bq_mlp_eval_desc;
+BQ_API int bq_mlp_eval(const bq_mlp_eval_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
