@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's metric on synthetic data.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3] [--cin 132]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3] [--cin 132] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,8 +9,10 @@ A "step" = one training pass (forward + backward + AdamW step) of the hot path o
 batch that is already resident in HBM: B=16 scenes x 40000 points (xyz + C_in features), and for
 workload c3 additionally one 512x512 view + question/answer ids per scene.  One process per GPU;
 each rank owns its own B=16 batch (weak scaling), gradients are all-reduced over RCCL.
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` for the dominant
-kernel and `cpu_baseline` (the CPU oracle port timed on a bounded sample; N=1 only).
+Rank 0 prints ONE JSON line: the headline (`value` in samples/s, `ms_per_step`) and the configuration it was measured on.
+That is all a plain run does after its timed steps.  `--full` adds, after the timed steps, what takes runs of its own:
+`roofline` for the dominant kernel and the per-kernel sub-rooflines (dedicated launches), `loop_reference` (the
+reference's unchanged loop, timed again) and `cpu_baseline` (the CPU oracle port timed on a bounded sample; N=1 only).
 `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy; that step starts from the seeded
 initial weights and a fresh optimizer (restored off the clock), so its inputs are the same in every run and two builds run
 with the same arguments can be compared array by array.
@@ -53,7 +55,10 @@ def parse():
     ap.add_argument("--batch", type=int, default=None, help="scenes per rank (default 16; c5: 32)")
     ap.add_argument("--points", type=int, default=None, help="points per scene (default 40000; c5: 80000)")
     ap.add_argument("--image", type=int, default=None, help="view side in pixels (default 512; c5: 1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: roofline and per-kernel "
+                         "figures from launches of their own, the reference's loop (loop_reference) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--no-geometry-prefetch", action="store_true",
                     help="c2: compute the sampling / grouping indices inside the step instead of one step ahead on a second stream")
     ap.add_argument("--dp-path", action="store_true", help="use the data-parallel step structure even on one GPU")
@@ -84,10 +89,11 @@ def parse():
     ap.add_argument("--eager-optimizer", dest="eager_optimizer", action="store_true",
                     help="reference loop: optimizer.step() launched eagerly (default: graphed.wrap_optimizer)")
     ap.add_argument("--no-loop-reference", dest="no_loop_reference", action="store_true",
-                    help="default c3 run: skip the second measurement (the reference's unchanged loop under graphed, "
+                    help="--full c3 run: skip the second measurement (the reference's unchanged loop under graphed, "
                          "reported as `loop_reference` on the same JSON line)")
-    ap.add_argument("--cpu-scenes", type=int, default=2, help="scenes in the bounded CPU-baseline sample")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0: min(os.cpu_count(), 32))")
+    ap.add_argument("--cpu-scenes", type=int, default=2, help="--full: scenes in the bounded CPU-baseline sample")
+    ap.add_argument("--cpu-threads", type=int, default=0,
+                    help="--full: threads of the CPU baseline (0: min(os.cpu_count(), 32))")
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16",
                     help="arithmetic of the dense layers: bf16 = the HIP kernel path (MFMA GEMMs, point-major detector); "
                          "f32 = the reference composition on torch ops (c2 only)")
@@ -1045,6 +1051,7 @@ def main():
         graphed = True
         for _ in range(2):
             step()
+    # (wrapped in every run, so that a plain run times the same launches as a --full one, which reports them as op_ms)
     timer = OpTimer()
     timer.wrap(_ext, ["furthest_point_sampling", "ball_query", "group_concat", "group_concat_grad"])
     torch.cuda.synchronize()
@@ -1069,7 +1076,9 @@ def main():
     dt = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, model, loss)   # (before the eager re-run below, which steps the optimizer again)
-    if graphed:
+    # A plain run launches nothing more on the GPU (a data-parallel run still checks its replicas, below).  What follows up to
+    # the reference's loop and the CPU baseline is --full only: per-kernel timings from launches of their own.
+    if args.full and graphed:
         # a replayed graph runs no Python, so the per-kernel HIP events are taken on an eager re-run of the same
         # step (same kernels, same stream) right after the timed region; it is not part of `value`
         if phased:
@@ -1087,7 +1096,7 @@ def main():
     timer.unwrap()
     # the same FPS launch with nothing else on the GPU (in the step it runs UNDER the image encoder's GEMMs)
     fps_alone_ms = float("nan")
-    if rank == 0:
+    if args.full and rank == 0:
         xyz_alone = batch["point_clouds"][..., :3].contiguous()
         _ext.furthest_point_sampling(xyz_alone, 2048)
         torch.cuda.synchronize()
@@ -1100,7 +1109,7 @@ def main():
         fps_alone_ms = ev0.elapsed_time(ev1) / 5
     # SA1's ball query (2048 centres x all points, radius 0.2, 64 samples) alone: the full grid and the background grid
     bq_alone_ms = bq_alone_bg_ms = float("nan")
-    if rank == 0:
+    if args.full and rank == 0:
         ctr = xyz_alone[:, :2048].contiguous()   # (any 2048 points serve as centres for the timing: the scan is exhaustive)
         for bg in (False, True):   # (bg: the exhaustive scan of rounds 3-4 for comparison -- the grid withdrawn)
             prev_min = _ext.BALL_QUERY_GRID_MIN_N[0]
@@ -1150,11 +1159,12 @@ def main():
     if rank == 0:
         print("host-side launch time per step: %.2f ms  [%s]" % (host_ms / args.steps, " ".join("%.1f" % h for h in host_each)), file=sys.stderr)
 
-    # the same model behind the reference's UNCHANGED loop, timed in this process right after the headline (INTEGRATION.md
+    # --full: the same model behind the reference's UNCHANGED loop, timed in this process right after the headline (INTEGRATION.md
     # section 3a; before the CPU baseline, whose 32 OpenMP threads keep spinning on the host): the phased step's graphs are
     # dropped first
     loop_ref_res, n_phase_graphs = None, (len(pipe.graphs or ()) if pipe is not None else 0)
-    if rank == 0 and phased and world == 1 and not args.no_loop_reference and args.workload != "c5" and not dp:
+    if (args.full and rank == 0 and phased and world == 1 and not args.no_loop_reference and args.workload != "c5"
+            and not dp):
         pipe.graphs, pipe._state = None, {}
         step = None
         pipe = None
@@ -1168,12 +1178,6 @@ def main():
             loop_ref_res = {"error": "%s: %s" % (type(e).__name__, e)}
 
     if rank == 0:
-        ops = timer.summary()
-        # dominant native kernel: SA1 furthest point sampling; algorithmic bytes 20*N*(m-1) per scene
-        key = ("furthest_point_sampling", (args.batch, args.points, 3))
-        fps_ms, _ = ops.get(key, (float("nan"), 0))
-        alg = 20.0 * args.points * (2048 - 1) * args.batch
-        achieved = alg / (fps_ms * 1e-3) / 1e9
         out = {
             "metric": ("train samples/s (%dk-pt scene + %d^2 view, bs%d)" % (args.points // 1000, args.image, args.batch)
                        if workload == "c3" else "train samples/s (40k-pt scene, DET stage only, bs16)"),
@@ -1194,55 +1198,64 @@ def main():
                                           % (sum(r.nbytes_on_wire() for r in reducers.values()) >> 20)) if phased
                                          else ("one packed bf16 all-reduce after the fwd+bwd graph, %d MB on the wire"
                                                % (reducer.nbytes_on_wire() >> 20))) if dp else None},
-            "roofline": None,      # filled below: the dominant dense kernel (MFMA GEMM)
-            "roofline_fps": {"kernel": "fps (SA1 %d->2048), csrc/fps_bucket.hip" % args.points, "bound": "hbm",
-                             "convention": "streaming-equivalent (SURVEY §8d), NOT physical traffic: 20*N*(m-1) bytes per "
-                                           "scene = what the reference's kernel streams; this kernel prunes ~41x of it "
-                                           "and is latency-bound (serial arg-max rounds)",
-                             "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": round(achieved / HBM_PEAK_GBS, 4), "ms_per_launch": round(fps_ms, 4),
-                             "rounds": 2047, "us_per_round": round(fps_ms * 1e3 / 2047, 3),
-                             "floor_us_per_round": 0.5, "floor_frac": round(0.5 / (fps_ms * 1e3 / 2047), 3),
-                             "traffic_from_profile": _fps_pmc() if (args.points == 40000 and args.batch == 16) else None,
-                             "timed_on": ("the timed steps (geometry phase launched eagerly between the graph replays)"
-                                          if phased else "eager re-run after the graph replay" if graphed
-                                          else "the timed steps"),
-                             "algorithmic_bytes_per_launch": alg,
-                             "alone": {"ms_per_launch": round(fps_alone_ms, 4),
-                                       "achieved": round(alg / (fps_alone_ms * 1e-3) / 1e9, 1),
-                                       "frac": round(alg / (fps_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                       "note": "5 back-to-back launches after the timed region, idle GPU"}},
-            "roofline_ballquery": ballquery_roofline(args, ops, bq_alone_ms, bq_alone_bg_ms, phased),
-            "op_ms": {"%s%s" % (k[0], list(k[1])): round(v[0], 4) for k, v in sorted(ops.items())},
-            "path_roofline": (lambda tm, det: {"t_min_ms": round(tm, 3), "frac": round(tm / (dt / args.steps * 1e3), 4),
-                                               **det})(*path_roofline(args, workload)),
         }
-        if workload == "c3":
-            per, tot_f, tot_ms, traffic, prof_frac = gemm_roofline(args, dev)
-            out["roofline"] = {"kernel": "bq::gemm128_kernel (csrc/gemm_mid.hip: forward / input-gradient forms, 256x128 tiles, "
-                                         "persistent, 2 workgroups per CU) + bq::gemm256_kernel (csrc/gemm.hip: weight gradients and, since round 6, the "
-                                         "forward / dX launches with a contraction >= 2304: fc2 forward, dX through fc1 and qkv): "
-                                         "the 8 launches of one ViT block (forward + dX, with the epilogues the step uses) + "
-                                         "the grouped dW launch of all 12 blocks", "bound": "mfma",
-                               "achieved": round(tot_f / tot_ms / 1e9, 1), "peak": 2500.0, "unit": "TFLOP/s",
-                               "frac": round(tot_f / tot_ms / 1e9 / 2500.0, 4),
-                               "frac_uses": "sum of the live HIP-event medians below (per_gemm[].us)",
-                               "from_profile_durations": prof_frac,
-                               "traffic": traffic,
-                               "algorithmic_flops": tot_f, "ms_total": round(tot_ms, 4), "per_gemm": per,
-                               "timed_on": "dedicated launches after the timed region, HIP events on the launch stream, "
-                                           "median of 10 (inside the step the same kernels replay from HIP graphs; the "
-                                           "in-step averages come from profiles/r06_c3_kernel_stats.csv, the counters from "
-                                           "profiles/r06_gemm_pmc.jsonl; both only at M = 16400, the shape they were taken at)"}
-            out["roofline_attn"] = attn_roofline(args, dev)
-        else:
-            out["roofline"] = out["roofline_fps"]
-        if world == 1 and args.workload != "c5":
-            out["roofline_det_bwd"] = det_bwd_roofline(args, dev)
-        if world == 1 and not args.no_cpu_baseline and args.workload != "c5":   # (c3 is the headline: its baseline is the one reported)
-            out["cpu_baseline"] = cpu_baseline(args, workload)
-        if loop_ref_res is not None:
-            out["loop_reference"] = loop_ref_res
+        if args.full:
+            ops = timer.summary()
+            # dominant native kernel: SA1 furthest point sampling; algorithmic bytes 20*N*(m-1) per scene
+            key = ("furthest_point_sampling", (args.batch, args.points, 3))
+            fps_ms, _ = ops.get(key, (float("nan"), 0))
+            alg = 20.0 * args.points * (2048 - 1) * args.batch
+            achieved = alg / (fps_ms * 1e-3) / 1e9
+            out.update({
+                "roofline": None,      # filled below: the dominant dense kernel (MFMA GEMM)
+                "roofline_fps": {"kernel": "fps (SA1 %d->2048), csrc/fps_bucket.hip" % args.points, "bound": "hbm",
+                                 "convention": "streaming-equivalent (SURVEY §8d), NOT physical traffic: 20*N*(m-1) bytes per "
+                                               "scene = what the reference's kernel streams; this kernel prunes ~41x of it "
+                                               "and is latency-bound (serial arg-max rounds)",
+                                 "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                 "frac": round(achieved / HBM_PEAK_GBS, 4), "ms_per_launch": round(fps_ms, 4),
+                                 "rounds": 2047, "us_per_round": round(fps_ms * 1e3 / 2047, 3),
+                                 "floor_us_per_round": 0.5, "floor_frac": round(0.5 / (fps_ms * 1e3 / 2047), 3),
+                                 "traffic_from_profile": _fps_pmc() if (args.points == 40000 and args.batch == 16) else None,
+                                 "timed_on": ("the timed steps (geometry phase launched eagerly between the graph replays)"
+                                              if phased else "eager re-run after the graph replay" if graphed
+                                              else "the timed steps"),
+                                 "algorithmic_bytes_per_launch": alg,
+                                 "alone": {"ms_per_launch": round(fps_alone_ms, 4),
+                                           "achieved": round(alg / (fps_alone_ms * 1e-3) / 1e9, 1),
+                                           "frac": round(alg / (fps_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                           "note": "5 back-to-back launches after the timed region, idle GPU"}},
+                "roofline_ballquery": ballquery_roofline(args, ops, bq_alone_ms, bq_alone_bg_ms, phased),
+                "op_ms": {"%s%s" % (k[0], list(k[1])): round(v[0], 4) for k, v in sorted(ops.items())},
+                "path_roofline": (lambda tm, det: {"t_min_ms": round(tm, 3), "frac": round(tm / (dt / args.steps * 1e3), 4),
+                                                   **det})(*path_roofline(args, workload)),
+            })
+            if workload == "c3":
+                per, tot_f, tot_ms, traffic, prof_frac = gemm_roofline(args, dev)
+                out["roofline"] = {"kernel": "bq::gemm128_kernel (csrc/gemm_mid.hip: forward / input-gradient forms, 256x128 tiles, "
+                                             "persistent, 2 workgroups per CU) + bq::gemm256_kernel (csrc/gemm.hip: weight gradients and, since round 6, the "
+                                             "forward / dX launches with a contraction >= 2304: fc2 forward, dX through fc1 and qkv): "
+                                             "the 8 launches of one ViT block (forward + dX, with the epilogues the step uses) + "
+                                             "the grouped dW launch of all 12 blocks", "bound": "mfma",
+                                   "achieved": round(tot_f / tot_ms / 1e9, 1), "peak": 2500.0, "unit": "TFLOP/s",
+                                   "frac": round(tot_f / tot_ms / 1e9 / 2500.0, 4),
+                                   "frac_uses": "sum of the live HIP-event medians below (per_gemm[].us)",
+                                   "from_profile_durations": prof_frac,
+                                   "traffic": traffic,
+                                   "algorithmic_flops": tot_f, "ms_total": round(tot_ms, 4), "per_gemm": per,
+                                   "timed_on": "dedicated launches after the timed region, HIP events on the launch stream, "
+                                               "median of 10 (inside the step the same kernels replay from HIP graphs; the "
+                                               "in-step averages come from profiles/r06_c3_kernel_stats.csv, the counters from "
+                                               "profiles/r06_gemm_pmc.jsonl; both only at M = 16400, the shape they were taken at)"}
+                out["roofline_attn"] = attn_roofline(args, dev)
+            else:
+                out["roofline"] = out["roofline_fps"]
+            if world == 1 and args.workload != "c5":
+                out["roofline_det_bwd"] = det_bwd_roofline(args, dev)
+            if world == 1 and not args.no_cpu_baseline and args.workload != "c5":   # (c3 is the headline: its baseline is the one reported)
+                out["cpu_baseline"] = cpu_baseline(args, workload)
+            if loop_ref_res is not None:
+                out["loop_reference"] = loop_ref_res
         if replicas_in_sync is not None:
             out["replicas_in_sync"] = replicas_in_sync
         if pipe is not None and reducers:

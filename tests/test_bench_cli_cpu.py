@@ -69,3 +69,12 @@ def test_dump_outputs_sample_is_fixed_aligned_and_bounded(tmp_path):
     # below the sample size every element is written, in order
     flat_b = torch.cat([t.reshape(-1).float() for t in (m[1].running_mean, m[1].running_var)])
     assert np.array_equal(a["buffers"], flat_b.numpy())
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """a plain run measures the headline alone; what takes runs of its own waits for --full"""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True

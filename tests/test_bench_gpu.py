@@ -72,3 +72,29 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
         assert x.shape == y.shape, n
         tol = 1e-6 * np.abs(x).max() + 1e-4 * np.abs(x)
         assert (np.abs(x - y) <= tol).all(), (n, float(np.abs(x - y).max()))
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_and_full_adds_the_rest():
+    """a plain one-GPU run ends at its headline: the line carries metric / value / unit / ms_per_step and nothing that takes
+    runs of its own; --full adds the rooflines, the per-kernel figures, the reference's loop and the CPU baseline (c3, small)"""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    moved = {"roofline", "roofline_fps", "roofline_ballquery", "roofline_attn", "roofline_det_bwd", "op_ms", "path_roofline",
+             "loop_reference", "cpu_baseline"}
+    for full in (False, True):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c3", "--batch", "2",
+                            "--points", "4096", "--image", "128", "--steps", "3", "--warmup", "1"] + (["--full"] if full else []),
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 2 * 1e3 / out["ms_per_step"]) <= 1e-2 * out["value"]
+        if full:
+            assert moved <= set(out), sorted(moved - set(out))
+            assert "error" not in out["loop_reference"], out["loop_reference"]
+            assert out["cpu_baseline"]["value"] > 0 and out["roofline"]["achieved"] > 0
+        else:
+            assert not moved & set(out), sorted(moved & set(out))
