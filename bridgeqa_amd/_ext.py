@@ -73,6 +73,47 @@ _lib.bq_twin_drop_add_ln_bwd.argtypes = [_vp] * 10 + [_i, _i, _f, _f, _u, _vp, _
 _lib.bq_twin_drop_add_ln_bwd.restype = ctypes.c_int
 _lib.bq_fps_workspace_bytes.argtypes = [_i, _i]
 _lib.bq_fps_workspace_bytes.restype = ctypes.c_size_t
+_lib.bq_drop_add_ln_bwd_det_slab_floats.argtypes = [_i, _i, _i]
+_lib.bq_drop_add_ln_bwd_det_slab_floats.restype = _l
+_lib.bq_drop_add_ln_bwd_det.argtypes = [_vp] * 4 + [_i] + [_vp] * 8 + [_i, _i, _f, _f, _f, _i, _u, _vp, _i, _vp]
+_lib.bq_drop_add_ln_bwd_det.restype = ctypes.c_int
+_lib.bq_gemm_splitk_fold_det.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp]
+_lib.bq_gemm_splitk_fold_det.restype = ctypes.c_int
+
+# ---- the deterministic training mode (bridgeqa_amd.set_deterministic) ------------------------------------------------------------
+# Every site of the training path where float atomics from several workgroups met on one address, the entry point that takes it in
+# the deterministic mode and the kernels that entry launches (none holds a float atomic: tests/test_deterministic_cpu.py reads their
+# ISA).  The dispatchers below call the entry named here.  Single adders onto a value an earlier launch stored (gemm `accum`, the
+# second row source of a weight gradient) were already reproducible; they run on gemm64_kernel_det too.
+DET_ROUTES = {
+    "ln_bwd": dict(entry="bq_drop_add_ln_bwd_det", src="ln.hip",
+                   kernels=("drop_add_ln_bwd_kernel_det", "ln_dgb_fold_det_kernel")),
+    "colsum_grouped": dict(entry="bq_colsum_grouped_det_bf16", src="gemm.hip",
+                           kernels=("colsum_grouped_det_kernel", "colsum_grouped_fold_det_kernel")),
+    # fp32-output small-tile GEMMs: cut contractions (the LM head's dH) into per-piece slabs, accum with plain stores
+    "gemm_splitk_f32": dict(entry="bq_gemm_bf16", src="gemm.hip", kernels=("gemm64_kernel_det",)),
+    "gemm_splitk_fold": dict(entry="bq_gemm_splitk_fold_det", src="gemm.hip", kernels=("splitk_fold_det_kernel",)),
+    # column sums in a bf16-output GEMM epilogue: the GEMM runs without them, the grouped fixed-order column sum takes them
+    "gemm_epilogue_colsum": dict(entry="bq_colsum_grouped_det_bf16", src="gemm.hip",
+                                 kernels=("colsum_grouped_det_kernel", "colsum_grouped_fold_det_kernel")),
+}
+
+
+def _det():
+    from . import is_deterministic
+    return is_deterministic()
+
+
+def _det_entry(site):
+    return getattr(_lib, DET_ROUTES[site]["entry"])
+
+
+def _ln_bwd_det(x, residual, gamma, gamma2, groups, dy, dsum, mean, rstd, dx, dres, dgb, M, H, eps, p_drop, p_path,
+                rows_per_sample, seed, seed_tensor, x_is_sum, what):
+    slab = torch.empty(max(1, _lib.bq_drop_add_ln_bwd_det_slab_floats(M, H, groups)), dtype=torch.float32, device=x.device)
+    _check(_det_entry("ln_bwd")(_p(x), _p(residual), _p(gamma), _p(gamma2), groups, _p(dy), _p(dsum), _p(mean), _p(rstd),
+                                _p(dx), _p(dres), _p(dgb), _p(slab), M, H, float(eps), float(p_drop), float(p_path),
+                                int(rows_per_sample), int(seed) & 0xFFFFFFFF, _p(seed_tensor), int(x_is_sum), _stream()), what)
 
 
 def library_path():
@@ -739,6 +780,10 @@ def drop_add_ln_bwd(x, residual, gamma, dy, mean, rstd, eps, p_drop, seed, seed_
         dres = torch.empty_like(x) if residual is not None else None
         if dgb is None:
             dgb = torch.zeros(2, H, dtype=torch.float32, device=x.device)
+        if _det():
+            _ln_bwd_det(x, residual, gamma, None, 1, dy, dsum, mean, rstd, dx, dres, dgb, M, H, eps, p_drop, p_path,
+                        rows_per_sample, seed, seed_tensor, 0, "drop_add_ln_bwd_det")
+            return dx, dres, dgb[0], dgb[1]
         _check(_lib.bq_drop_add_ln_bwd(_p(x), _p(residual), _p(gamma), _p(dy), _p(dsum), _p(mean), _p(rstd), _p(dx),
                                        _p(dres), _p(dgb), M, H, float(eps), float(p_drop), float(p_path),
                                        int(rows_per_sample), int(seed) & 0xFFFFFFFF, _p(seed_tensor), _stream()),
@@ -756,6 +801,10 @@ def drop_add_ln_bwd_sum(s, gamma, dy, mean, rstd, eps, seed, seed_tensor, dsum=N
         dres = torch.empty_like(s) if p_path > 0 else None
         if dgb is None:
             dgb = torch.zeros(2, H, dtype=torch.float32, device=s.device)
+        if _det():
+            _ln_bwd_det(s, None, gamma, None, 1, dy, dsum, mean, rstd, dx, dres, dgb, M, H, eps, 0.0, p_path, rows_per_sample,
+                        seed, seed_tensor, 1, "drop_add_ln_bwd_sum_det")
+            return dx, (dres if dres is not None else dx), dgb[0], dgb[1]
         _check(_lib.bq_drop_add_ln_bwd_sum(_p(s), _p(gamma), _p(dy), _p(dsum), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dgb),
                                            M, H, float(eps), float(p_path), int(rows_per_sample), int(seed) & 0xFFFFFFFF,
                                            _p(seed_tensor), _stream()), "drop_add_ln_bwd_sum")
@@ -787,6 +836,10 @@ def twin_drop_add_ln_bwd(x, residual, gamma, gamma2, dy, mean, rstd, eps, p_drop
         dres = torch.empty_like(x) if residual is not None else None
         if dgb is None:
             dgb = torch.zeros(2, 2, H, dtype=torch.float32, device=x.device)
+        if _det():
+            _ln_bwd_det(x, residual, gamma, gamma2, 2, dy, None, mean, rstd, dx, dres, dgb, M, H, eps, p_drop, 0.0, 0, seed,
+                        seed_tensor, 0, "twin_drop_add_ln_bwd_det")
+            return dx, dres, dgb
         _check(_lib.bq_twin_drop_add_ln_bwd(_p(x), _p(residual), _p(gamma), _p(gamma2), _p(dy), _p(mean), _p(rstd),
                                             _p(dx), _p(dres), _p(dgb), M, H, float(eps), float(p_drop),
                                             int(seed) & 0xFFFFFFFF, _p(seed_tensor), _stream()), "twin_drop_add_ln_bwd")
@@ -878,6 +931,7 @@ def fuse_point_features(pix, feat, maxpool):
 # ---- MFMA bf16 GEMM family (csrc/gemm.hip) ------------------------------------------------------------
 GEMM_P_XC, GEMM_Q_XC, GEMM_OUT_F32, GEMM_BACKGROUND = 1, 2, 4, 8
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_CE, EPI_ADD = 0, 1, 2, 3, 4, 5
+GEMM_DET = 16   # BQ_GEMM_DET: set by gemm_grouped itself in the deterministic mode
 
 
 class _GemmDesc(ctypes.Structure):
@@ -944,9 +998,15 @@ def gemm_grouped(problems, flags, epilogue=EPI_NONE, tile=None):
     """One launch for a list of problems out[j][i] = epilogue(sum_kc P(i,kc) Q(j,kc)) (include/bqhip_fusion.h,
     bq_gemm_bf16).  problems: dicts with P, Q, out (2-D tensors, contiguous last dim) and optional bias (fp32 (Ni,)),
     out2, aux, colsum (fp32 (Ni,), accumulated).  P: (Ni, Kc), or (Kc, Ni) with GEMM_P_XC; Q likewise over j."""
+    if _det():
+        return _gemm_grouped_det(problems, flags, epilogue, tile)
+    return _gemm_grouped_launch(problems, flags, epilogue, tile)
+
+
+def _gemm_grouped_launch(problems, flags, epilogue, tile):
+    pxc, qxc, f32 = bool(flags & GEMM_P_XC), bool(flags & GEMM_Q_XC), bool(flags & GEMM_OUT_F32)
     n = len(problems)
     arr = (_GemmDesc * n)()
-    pxc, qxc, f32 = bool(flags & GEMM_P_XC), bool(flags & GEMM_Q_XC), bool(flags & GEMM_OUT_F32)
     t_auto = 32
     any_map = False
     for k, pr in enumerate(problems):
@@ -1008,6 +1068,39 @@ def gemm_grouped(problems, flags, epilogue=EPI_NONE, tile=None):
         if (tile or t_auto) == 128 and n == 1 and (STREAMK[0] or STREAMK256[0]):
             _streamk_workspace(dev)
         _check(_lib.bq_gemm_bf16(arr, n, int(flags), int(epilogue), int(tile or t_auto), _stream()), "gemm_bf16")
+
+
+def _gemm_grouped_det(problems, flags, epilogue, tile):
+    """gemm_grouped in the deterministic mode (DET_ROUTES): the launch carries GEMM_DET; a cut fp32 contraction (ksplit > 1) runs
+    into per-piece slabs that bq_gemm_splitk_fold_det adds onto `out` in piece order; column sums of a bf16 output are taken
+    after the launch by the grouped fixed-order column sum.  Refuses what has no fixed-order form: stream-K, a cut contraction
+    with column sums."""
+    if STREAMK[0] or STREAMK256[0]:
+        raise RuntimeError("gemm: stream-K is on (streamk_enable / streamk256_enable) while the deterministic mode is on")
+    f32 = bool(flags & GEMM_OUT_F32)
+    probs, folds, sums = [], [], []
+    for pr in problems:
+        ks = int(pr.get("ksplit", 1))
+        if epilogue != EPI_BIAS_CE and ks > 1:
+            out = pr["out"]
+            if not f32 or pr.get("colsum") is not None or pr.get("accum") or out.dim() != 2 or out.stride(1) != 1:
+                raise RuntimeError("gemm: a cut contraction in the deterministic mode needs fp32 plain-row out, no colsum or accum")
+            slab = torch.empty(ks, out.shape[0], out.stride(0), dtype=torch.float32, device=out.device)
+            folds.append((slab, out, ks))
+            pr = dict(pr, out=slab[0, :, :out.shape[1]])
+        elif not f32 and epilogue != EPI_BIAS_CE and pr.get("colsum") is not None:
+            sums.append((pr["out"], pr["colsum"]))
+            pr = dict(pr, colsum=None)
+        probs.append(pr)
+    _gemm_grouped_launch(probs, flags | GEMM_DET, epilogue, tile)
+    for slab, out, ks in folds:
+        R, C = out.shape
+        with torch.cuda.device(out.device):
+            _check(_det_entry("gemm_splitk_fold")(_p(slab), _p(out), None, ks, R, C, out.stride(0), _stream()),
+                   "gemm_splitk_fold_det")
+    if sums:
+        _colsum_grouped_into([o.reshape(-1, o.shape[-1]) if o.dim() == 3 else o for o, _ in sums], [c for _, c in sums],
+                             "gemm_epilogue_colsum")
 
 
 # ---- stream-K workspaces (bq_gemm_set_workspace): one per (device, stream), allocated at the first tile-128 single-problem
@@ -1110,11 +1203,43 @@ _lib.bq_colsum_grouped_bf16.argtypes = [ctypes.POINTER(_ColsumDesc), _i, _vp]
 _lib.bq_colsum_grouped_bf16.restype = ctypes.c_int
 
 
+_lib.bq_colsum_grouped_det_floats.argtypes = [ctypes.POINTER(_ColsumDesc), _i]
+_lib.bq_colsum_grouped_det_floats.restype = _l
+_lib.bq_colsum_grouped_det_bf16.argtypes = [ctypes.POINTER(_ColsumDesc), _i, _vp, _vp]
+_lib.bq_colsum_grouped_det_bf16.restype = ctypes.c_int
+
+
+def _colsum_grouped_into(mats, outs, site):
+    """outs[p] += the column sums of mats[p] (bf16 (M_p, N_p), fp32 (N_p,) contiguous) in the fixed-order form of the
+    deterministic mode: partials per 512-row block, folded in row-block order by a second launch"""
+    n = len(mats)
+    arr = (_ColsumDesc * n)()
+    for k, (m, o) in enumerate(zip(mats, outs)):
+        _mat(m, "g")
+        if m.dtype != torch.bfloat16 or o.dtype != torch.float32 or not o.is_contiguous() or o.numel() != m.shape[1]:
+            raise RuntimeError("colsum_grouped: bf16 (M, N) matrices into contiguous fp32 (N,) sums")
+        arr[k].g, arr[k].out, arr[k].M, arr[k].N, arr[k].ld = m.data_ptr(), o.data_ptr(), m.shape[0], m.shape[1], m.stride(0)
+    dev = mats[0].device
+    with torch.cuda.device(dev):
+        part = torch.empty(max(1, _lib.bq_colsum_grouped_det_floats(arr, n)), dtype=torch.float32, device=dev)
+        _check(_det_entry(site)(arr, n, _p(part), _stream()), "colsum_grouped_det")
+
+
 def colsum_grouped(mats):
     """fp32 column sums of several bf16 (M_p, N_p) matrices (contiguous last dim) in one launch; returns a list of
-    (N_p,) views of ONE zero-initialised buffer (one memset + one kernel for all bias gradients of a backward pass)"""
+    (N_p,) views of ONE zero-initialised buffer (one memset + one kernel for all bias gradients of a backward pass;
+    in the deterministic mode a fixed-order fold as a second launch instead of float atomics)"""
     n = len(mats)
     dev = mats[0].device
+    if _det():
+        with torch.cuda.device(dev):
+            flat = torch.zeros(sum(m.shape[1] for m in mats), dtype=torch.float32, device=dev)
+        outs, off = [], 0
+        for m in mats:
+            outs.append(flat[off:off + m.shape[1]])
+            off += m.shape[1]
+        _colsum_grouped_into(mats, outs, "colsum_grouped")
+        return outs
     with torch.cuda.device(dev):
         flat = torch.zeros(sum(m.shape[1] for m in mats), dtype=torch.float32, device=dev)
         arr = (_ColsumDesc * n)()

@@ -607,260 +607,20 @@ namespace bq {
 
 // NS = LDS stages (NS - 1 K tiles in flight).  MEASURED: 5 instead of 3 changes nothing for the detector's cut
 // contractions either (tools/bench_det_wgrad.py, to 0.1 us) -- they were bound by their atomics, not by bytes in flight
+// DET (gemm64_kernel_det, the deterministic training mode, bq_gemm_bf16 with BQ_GEMM_DET): no float atomics anywhere.  A cut
+// contraction (ksplit > 1) stores piece ks into its own slab out + ks * Nj * ldo with plain stores (bq_gemm_splitk_fold_det
+// sums the slabs in piece order afterwards); accum adds onto what an earlier launch stored with a plain load + add + store --
+// the ONE adder of every such address in the launch, so the bits are those of the atomic form.
 template <int BJ, bool P_XC, bool Q_XC, int EPI, bool OUT_F32, int KT = 1, int NS = 3>
 __global__ __launch_bounds__(256) void gemm64_kernel(const GemmArgs args) {
-  static_assert(BJ == 64 || (BJ == 32 && !Q_XC), "32-wide j tiles only for K-contiguous Q");
-  static_assert(KT == 1 || KT == 2 || (KT == 4 && BJ == 32), "one, two or (32-row tiles) four K tiles per step");
-  constexpr int QF = BJ / 32;               // 16-wide j fragments per wave
-  constexpr int Q_UNIT = BJ * 128;          // bytes of the Q image per K tile
-  constexpr int TILE_BYTES = 8192 + Q_UNIT;
-  constexpr int STAGE = KT * TILE_BYTES;
-  // NS LDS stages, NS - 1 K tiles in flight.  MEASURED (profiles/r02_gemm_bench_v2.json): 5 stages instead of 3 change
-  // nothing for the forward / dX forms (a K tile costs ~0.24 us either way: the loop is bound by the ISSUE of its 3-4
-  // LDS-DMA instructions per wave, ~100 cycles each, not by memory latency) and halve the weight-gradient form
-  // (80 KB of LDS = 2 workgroups per CU for a kernel that lives on its output stores) => 3.
-  static_assert(NS >= 3 && NS * STAGE <= 160 * 1024, "LDS stages");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[NS * STAGE];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 1, wc = wave & 1;
-
-  const int t = blockIdx.x;
-  int pi = 0;
-  for (int k = 1; k < args.n; ++k)
-    if (t >= args.p[k].tile0) pi = k;
-  const GemmProblem &pr = args.p[pi];
-  const int ksplit = OUT_F32 ? pr.ksplit() : 1;
-  const int Ni = pr.Ni, Nj = pr.Nj, Kc = pr.Kc;
-  int tl = t - pr.tile0, ks = 0;
-  if (ksplit > 1) {
-    // a cut contraction (detector weight gradients: millions of rows, 1 - 8 output tiles): the output tiles of ONE piece
-    // read the same rows of both operands, so they get neighbouring slots of the same XCD (workgroups go to the XCDs
-    // round-robin by blockIdx) and meet in its L2 (PMC: operands fetched once) -- 170 -> 125 us on SA2's first layer
-    // against the piece-major order that spreads them over the XCDs
-    const int lt = t - pr.tile0;
-    const int ntl = pr.tiles_i() * ((Nj + BJ - 1) / BJ);
-    if ((ksplit & 7) == 0 && (pr.tile0 & 7) == 0) {
-      const int slot = lt >> 3;
-      tl = slot % ntl;
-      ks = (slot / ntl) * 8 + (lt & 7);
-    } else {
-      tl = lt % ntl;
-      ks = lt / ntl;
-    }
-  }
-  const int bj = tl / pr.tiles_i(), bi = tl % pr.tiles_i();
-  const int i0 = bi * 64, j0 = bj * BJ;
-  const int ldp = pr.ldp, ldq = pr.ldq;
-  const int nkt_all = (Kc + 63) >> 6;
-  const int kt_per = (nkt_all + ksplit - 1) / ksplit;
-  const int kt0 = ks * kt_per;                         // this workgroup's K tiles: [kt0, kt0 + nkt)
-  const int nkt = max(0, min(kt_per, nkt_all - kt0));
-
-  const auto rsP = __builtin_amdgcn_make_buffer_rsrc((void *)pr.P, 0, pr.p_bytes, 0x00020000);
-  const auto rsQ = __builtin_amdgcn_make_buffer_rsrc((void *)pr.Q, 0, pr.q_bytes, 0x00020000);
-  const int cp = lane & 7;
-  // P unit: 2 DMAs per wave (rows (2w+d)*8 + lane/8); Q unit: 2 (BJ = 64) or 1 (BJ = 32: rows w*8 + lane/8)
-  unsigned vp[2], vq[2];
-  // XC Q under a row map (short contractions over a strided (batch, rows) view): the contraction row each DMA stages next
-  // and its column offset.  SCALARS on purpose: as small arrays hipcc promoted them to LDS (+ 4 KB per workgroup) and every
-  // gemm64 launch of the step got 10-20 us slower (profiles/r04: 15.2 -> 27.1 us on the text side's dX form)
-  const bool q_xc_map = Q_XC && pr.q_rpb() != 0;   // (workgroup-uniform)
-  int qrow0 = 0, qrow1 = 0;
-  unsigned qcol0 = 0, qcol1 = 0;
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    const int ur = (wave * 2 + d) * 8 + (lane >> 3);
-    if (!P_XC) vp[d] = (unsigned)(((i0 + ur) * ldp + (cp ^ (ur & 7)) * 8) * 2);
-    else vp[d] = (unsigned)((ur * ldp + i0 + (cp ^ (xg(ur) << 1)) * 8) * 2);
-    const int uq = (BJ == 64) ? ur : wave * 8 + (lane >> 3);
-    // (batched-row map of Q, GemmProblem::q_rpb: on its j rows here, on its contraction rows in the XC form -- see stage())
-    if (!Q_XC) vq[d] = (mapped_row(j0 + uq, ldq, pr.q_rpb(), pr.q_bstride) + (unsigned)((cp ^ (uq & 7)) * 8)) * 2u;
-    else vq[d] = (unsigned)((uq * ldq + j0 + (cp ^ (xg(uq) << 1)) * 8) * 2);
-    if (Q_XC) {
-      const int row = kt0 * 64 + uq;
-      const unsigned col = (unsigned)(j0 + (cp ^ (xg(uq) << 1)) * 8);
-      if (d == 0) { qrow0 = row; qcol0 = col; } else { qrow1 = row; qcol1 = col; }
-    }
-  }
-  const unsigned p_step = P_XC ? (unsigned)(64 * ldp * 2) : 128u;
-  const unsigned q_step = Q_XC ? (unsigned)(64 * ldq * 2) : 128u;
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    vp[d] += (unsigned)kt0 * p_step;
-    vq[d] += (unsigned)kt0 * q_step;
-  }
-  constexpr int NDMA = KT * (2 + (BJ == 64 ? 2 : 1));  // LDS-DMAs per wave per step
-
-  auto stage = [&](int step) {
-#pragma unroll
-    for (int h = 0; h < KT; ++h) {
-      const bool live = step * KT + h < nkt;
-      const unsigned base = (unsigned)((step % NS) * STAGE + h * TILE_BYTES);
-#pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsP, (lds_void_t *)(smem + base + (wave * 2 + d) * 1024), 16,
-                                                 live ? vp[d] : 0x80000000u, 0, 0, 0);
-        vp[d] += p_step;
-      }
-#pragma unroll
-      for (int d = 0; d < (BJ == 64 ? 2 : 1); ++d) {
-        const int blk = (BJ == 64) ? wave * 2 + d : wave;
-        if (Q_XC && q_xc_map) {   // short contractions over a strided (batch, rows) view: one division per DMA
-          if (d == 0) { vq[0] = (mapped_row(qrow0, ldq, pr.q_rpb(), pr.q_bstride) + qcol0) * 2u; qrow0 += 64; }
-          else { vq[1] = (mapped_row(qrow1, ldq, pr.q_rpb(), pr.q_bstride) + qcol1) * 2u; qrow1 += 64; }
-        }
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lds_void_t *)(smem + base + 8192 + blk * 1024), 16,
-                                                 live ? vq[d] : 0x80000000u, 0, 0, 0);
-        vq[d] += q_step;
-      }
-    }
-  };
-
-  const int row16 = lane & 15, q4 = lane >> 4;
-  const int kc_base = row16 * 128 + ((q4 ^ (row16 & 7)) << 4);
-  // (XC fragment addresses in closed form: read_frag_cf, gemm_common.h -- sub16 depends on the wave here)
-  const int xc_q = (lane & 15) >> 2, xcg = (xc_q >> 1) | ((q4 & 1) << 1);
-  const int xc0 = (8 * q4 + xc_q) * 128 + 8 * (lane & 3);
-
-  f32x4 acc[2][QF];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < QF; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // weight-gradient form with pr.colsum set: the column sums of Q over this workgroup's share of the contraction (the
-  // bias gradient) from all-ones MFMAs on the B fragments, waves wr == 0 of the i = 0 tiles (see gemm256_kernel)
-  constexpr bool QSUM = P_XC && Q_XC && OUT_F32;
-  const bool do_qsum = QSUM && pr.colsum != nullptr && bi == 0 && wr == 0;   // wave-uniform
-  f32x4 qs[QF];
-  bf16x8 ones;
-#pragma unroll
-  for (int b = 0; b < QF; ++b) qs[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-
-#pragma unroll
-  for (int p = 0; p < NS - 1; ++p) stage(p);
-  const int nsteps = (nkt + KT - 1) / KT;
-  for (int step = 0; step < nsteps; ++step) {
-    // step `step` has landed for this wave (steps step+1 .. step+NS-2 may still be in flight); after the barrier: for
-    // every wave, and every wave has finished reading the buffer that step step+NS-1 is about to overwrite
-    static_assert((NS - 2) * NDMA <= 63, "vmcnt is a 6-bit counter");
-    wait_vmcnt<(NS - 2) * NDMA>();
-    BQ_BARRIER();
-    stage(step + NS - 1);
-#pragma unroll
-    for (int h = 0; h < KT; ++h) {  // (a K tile past the end was staged as zeros: it adds nothing)
-      const unsigned char *buf = smem + (step % NS) * STAGE + h * TILE_BYTES;
-      bf16x8 fa[2][2], fb[QF][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) fa[a][kk] = read_frag_cf_x<P_XC>(buf, wr * 2 + a, kk, kc_base, xc0, xcg);
-#pragma unroll
-      for (int b = 0; b < QF; ++b)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) fb[b][kk] = read_frag_cf_x<Q_XC>(buf + 8192, wc * QF + b, kk, kc_base, xc0, xcg);
-      if (P_XC || Q_XC) {
-        // (round 6) the contraction-major reads are inline asm: behind stage() hipcc fenced them with vmcnt(0) -- every step
-        // of the weight-gradient forms waited for the DMAs it had just issued for step + NS - 1 (tools/isa_waits.py)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < QF; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][kk], fb[b][kk], acc[a][b], 0, 0, 0);
-      if (QSUM && do_qsum) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-          for (int b = 0; b < QF; ++b) qs[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fb[b][kk], qs[b], 0, 0, 0);
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  // ---- epilogue: straight from the accumulators (8-B bf16 / 16-B fp32 pieces of an output row) ---------------------
-  const int ldo = pr.ldo;
-  const int iw = i0 + wr * 32, jw = j0 + wc * (BJ / 2);
-  const bool atomic_out = ksplit > 1 || pr.accum();   // fp32 out: add to what is there (cut contraction / second row source)
-  if (QSUM && do_qsum && q4 == 0) {
-#pragma unroll
-    for (int b = 0; b < QF; ++b) {
-      const int j = jw + b * 16 + row16;
-      if (j < Nj) {
-        if (!atomic_out) pr.colsum[j] = qs[b][0];
-        else atomicAdd(pr.colsum + j, qs[b][0]);   // (zero-initialised by the caller, as `out` is)
-      }
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    const int i = iw + a * 16 + q4 * 4;
-    float b4[4] = {0.f, 0.f, 0.f, 0.f};
-    if ((EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) && pr.bias != nullptr && i < Ni) load_bias4(pr, i, b4);
-    float cs[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int b = 0; b < QF; ++b) {
-      const int j = jw + b * 16 + row16;
-      const bool ok = j < Nj && i < Ni;
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = acc[a][b][r] + b4[r];
-      // element offset of row j of out / out2 / aux (64-bit on plain rows: outputs beyond 2 G elements exist)
-      const long jo = pr.o_rpb() ? (long)mapped_row(j < Nj ? j : 0, ldo, pr.o_rpb(), pr.o_bstride) : (long)j * ldo;
-      if (OUT_F32) {
-        float *dst = reinterpret_cast<float *>(pr.out) + jo + i;
-        if (ok && !atomic_out) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-        if (ok && atomic_out) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) atomicAdd(dst + r, v[r]);
-        }
-        continue;
-      }
-      if (EPI == EPI_DGELU && ok) {
-        const bf16x4 y = *reinterpret_cast<const bf16x4 *>(pr.aux + jo + i);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= dgelu_f((float)y[r]);
-      }
-      if (EPI == EPI_ADD && ok) {
-        const bf16x4 y = *reinterpret_cast<const bf16x4 *>(pr.aux + jo + i);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += (float)y[r];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = (float)(__bf16)v[r];
-      if (ok) {
-        uint2 pk;
-        pk.x = pack_bf16x2(v[0], v[1]);
-        pk.y = pack_bf16x2(v[2], v[3]);
-        *reinterpret_cast<uint2 *>(reinterpret_cast<__bf16 *>(pr.out) + jo + i) = pk;
-        if (EPI == EPI_BIAS_GELU) {
-          pk.x = pack_bf16x2(gelu_f(v[0]), gelu_f(v[1]));
-          pk.y = pack_bf16x2(gelu_f(v[2]), gelu_f(v[3]));
-          *reinterpret_cast<uint2 *>(reinterpret_cast<__bf16 *>(pr.out2) + jo + i) = pk;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) cs[r] += ok ? v[r] : 0.f;
-    }
-    if (!OUT_F32 && pr.colsum != nullptr) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s = cs[r];
-        s += dpp_f32_add<0x111>(s);
-        s += dpp_f32_add<0x112>(s);
-        s += dpp_f32_add<0x114>(s);
-        s += dpp_f32_add<0x118>(s);
-        if (row16 == 15 && i + r < Ni) atomicAdd(pr.colsum + i + r, s);
-      }
-    }
-  }
+  constexpr bool DET = false;
+#include "gemm64_kernel_body.h"
+}
+template <int BJ, bool P_XC, bool Q_XC, int EPI>
+__global__ __launch_bounds__(256) void gemm64_kernel_det(const GemmArgs args) {
+  constexpr bool OUT_F32 = true, DET = true;
+  constexpr int KT = 1, NS = 3;
+#include "gemm64_kernel_body.h"
 }
 
 
@@ -1432,34 +1192,55 @@ struct ColsumArgs {
   ColsumProblem p[COLSUM_MAX_PROBLEMS];
 };
 
+// DET (colsum_grouped_det_kernel): workgroup t stores its 256 column totals to partial[t * 256 ..] with plain stores instead,
+// and colsum_grouped_fold_det_kernel adds the row blocks of every column in row-block order (a second launch: stream order
+// makes the partials visible, no fence).
 __global__ __launch_bounds__(256) void colsum_grouped_kernel(const ColsumArgs args) {
-  __shared__ float red[8][256];
-  const int t = blockIdx.x;
-  int pi = 0;
-  for (int k = 1; k < args.n; ++k)
-    if (t >= args.p[k].wg0) pi = k;
+  constexpr bool DET = false;
+  float *const partial = nullptr;
+#include "colsum_grouped_kernel_body.h"
+}
+__global__ __launch_bounds__(256) void colsum_grouped_det_kernel(const ColsumArgs args, float *partial) {
+  constexpr bool DET = true;
+#include "colsum_grouped_kernel_body.h"
+}
+// out_p[n] += sum over row blocks rb = 0, 1, ... of partial[(wg0 + rb * cblocks + n / 256) * 256 + n % 256]: one workgroup per
+// (problem, 256-column block), one column per thread, row blocks in ascending order
+__global__ __launch_bounds__(256) void colsum_grouped_fold_det_kernel(const ColsumArgs args, const float *__restrict__ partial) {
+  int b = blockIdx.x, pi = 0;
+  while (pi + 1 < args.n && b >= args.p[pi].cblocks) b -= args.p[pi++].cblocks;
   const ColsumProblem &pr = args.p[pi];
-  const int tl = t - pr.wg0;
-  const int cb = tl % pr.cblocks, rb = tl / pr.cblocks;
-  const int tc = threadIdx.x & 31, tr = threadIdx.x >> 5;
-  const int col = cb * 256 + tc * 8;
-  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (col < pr.N) {  // N % 8 == 0
-    const int r1 = min(pr.M, (rb + 1) * COLSUM_ROWS);
-    for (int r = rb * COLSUM_ROWS + tr; r < r1; r += 8) {
-      const bf16x8 v = *reinterpret_cast<const bf16x8 *>(pr.g + (long)r * pr.ld + col);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s[e] += (float)v[e];
-    }
+  const int col = b * 256 + threadIdx.x;
+  if (col >= pr.N) return;
+  const int rblocks = (pr.M + COLSUM_ROWS - 1) / COLSUM_ROWS;
+  const float *src = partial + ((long)pr.wg0 + b) * 256 + threadIdx.x;
+  float t = 0.f;
+  for (int rb = 0; rb < rblocks; ++rb) t += src[(long)rb * pr.cblocks * 256];
+  pr.out[col] = pr.out[col] + t;
+}
+
+// The fold of a cut fp32 contraction of the deterministic mode (gemm64_kernel_det with ksplit > 1): out[r][c] += slab_0[r][c] +
+// slab_1[r][c] + ... in piece order, slab_p = slab + p * rows * ld; out_bf16 (same layout, may be NULL) also receives the sum
+// rounded to bf16.  One element of four columns per thread.
+__global__ __launch_bounds__(256) void splitk_fold_det_kernel(const float *__restrict__ slab, float *out, __bf16 *out_bf16,
+                                                              int pieces, int rows, int cols, int ld) {
+  const long n4 = (long)rows * (cols / 4);
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n4) return;
+  const int r = (int)(e / (cols / 4)), c = (int)(e % (cols / 4)) * 4;
+  const long off = (long)r * ld + c, stride = (long)rows * ld;
+  float4 t = out ? *reinterpret_cast<const float4 *>(out + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int p = 0; p < pieces; ++p) {
+    const float4 v = *reinterpret_cast<const float4 *>(slab + p * stride + off);
+    t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[tr][tc * 8 + e] = s[e];
-  __syncthreads();
-  const int c = threadIdx.x;
-  float tot = 0.f;
-#pragma unroll
-  for (int g8 = 0; g8 < 8; ++g8) tot += red[g8][c];
-  if (cb * 256 + c < pr.N) atomicAdd(pr.out + cb * 256 + c, tot);
+  if (out) *reinterpret_cast<float4 *>(out + off) = t;
+  if (out_bf16) {
+    uint2 pk;
+    pk.x = pack_bf16x2(t.x, t.y);
+    pk.y = pack_bf16x2(t.z, t.w);
+    *reinterpret_cast<uint2 *>(out_bf16 + off) = pk;
+  }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -1506,13 +1287,36 @@ static int launch_variant(const GemmArgs &ga, int tile, hipStream_t st, bool lon
   return 0;
 }
 
+// BQ_GEMM_DET: the fp32-output forms of the small-tile kernel (the only ones with float atomics: cut contractions, accum) run
+// on gemm64_kernel_det; every other form the deterministic mode may launch stores plainly (bf16-output column sums and
+// stream-K are refused by bq_gemm_bf16)
+template <bool P_XC, bool Q_XC, int EPI>
+static int launch_det_variant(const GemmArgs &ga, int tile, hipStream_t st) {
+  if (tile == 64) {
+    hipLaunchKernelGGL((gemm64_kernel_det<64, P_XC, Q_XC, EPI>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
+    return 0;
+  }
+  if constexpr (!Q_XC) {
+    hipLaunchKernelGGL((gemm64_kernel_det<32, P_XC, Q_XC, EPI>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
+    return 0;
+  }
+  return -1;
+}
+
 static int launch_gemm(const GemmArgs &ga, int flags, int epi, int tile, hipStream_t st) {
   const bool pxc = flags & BQ_GEMM_P_XC, qxc = flags & BQ_GEMM_Q_XC, f32 = flags & BQ_GEMM_OUT_F32;
+  if ((flags & BQ_GEMM_DET) && f32 && tile != 256 && tile != 128) {
+    if (!pxc && !qxc && epi == EPI_NONE) return launch_det_variant<false, false, EPI_NONE>(ga, tile, st);
+    if (!pxc && !qxc && epi == EPI_BIAS) return launch_det_variant<false, false, EPI_BIAS>(ga, tile, st);
+    if (pxc && !qxc && epi == EPI_NONE) return launch_det_variant<true, false, EPI_NONE>(ga, tile, st);
+    if (pxc && qxc && epi == EPI_NONE) return launch_det_variant<true, true, EPI_NONE>(ga, tile, st);
+    return -1;
+  }
   // measured on the c3 step (A/B in one call): never 46.2 ms, from 24 K tiles 45.5-45.9, from 12 K tiles 45.3-45.6
   constexpr int long_k_tiles = 12;
   bool long_k = long_k_tiles > 0 && tile != 256 && ga.total_tiles <= 2048;
   for (int k = 0; k < ga.n; ++k) long_k = long_k && ga.p[k].Kc >= 64 * long_k_tiles;
-  if (tile == 128 && (gemm_sk_mode() & 2) && !(flags & BQ_GEMM_BACKGROUND) && ga.n == 1 && !pxc && !qxc && !f32 &&
+  if (tile == 128 && (gemm_sk_mode() & 2) && !(flags & (BQ_GEMM_BACKGROUND | BQ_GEMM_DET)) && ga.n == 1 && !pxc && !qxc && !f32 &&
       (epi == EPI_NONE || epi == EPI_BIAS) && ga.p[0].colsum == nullptr && ga.p[0].q_rpb() == 0 && ga.p[0].o_rpb() == 0) {
     // stream-K on the 256 x 256 kernel (header of gemm256_kernel): one problem with a long contraction whose 256 x 256 tiles
     // would leave >= 15 % of a one-workgroup-per-CU grid idle, every share still >= 16 K tiles
@@ -1573,6 +1377,9 @@ extern "C" int bq_gemm_bf16(const bq_gemm_desc *d, int n, int flags, int epilogu
              "bq_gemm_bf16: tile must be 256, 128 (= 256 x 128), 64 or 32 (got %d)", tile);
   const bool pxc = flags & BQ_GEMM_P_XC, qxc = flags & BQ_GEMM_Q_XC, f32 = flags & BQ_GEMM_OUT_F32;
   BQ_REQUIRE(!(flags & BQ_GEMM_BACKGROUND) || tile == 128, BQ_EINVAL, "bq_gemm_bf16: BQ_GEMM_BACKGROUND needs tile 128");
+  const bool det = flags & BQ_GEMM_DET;
+  BQ_REQUIRE(!det || tile != 128 || gemm_sk_mode() == 0, BQ_EINVAL,
+             "bq_gemm_bf16: BQ_GEMM_DET with a stream-K mode on (bq_gemm_streamk_mode)");
   hipStream_t st = (hipStream_t)stream;
   int done = 0;
   while (done < n) {
@@ -1627,6 +1434,11 @@ extern "C" int bq_gemm_bf16(const bq_gemm_desc *d, int n, int flags, int epilogu
       // operand bytes (plus the rows of a ragged edge tile) must stay below the out-of-range sentinel of the DMA offsets
       BQ_REQUIRE(pb + (long)ti * s.ldp * 2 < 0x7FFFFFFFL && qb + (long)tj * s.ldq * 2 + (s.q_rpb > 0 ? 2L * s.q_bstride * 2 : 0) < 0x7FFFFFFFL,
                  BQ_EINVAL, "bq_gemm_bf16: operand larger than 2 GB (problem %d)", done);
+      // the deterministic mode: no float atomic may receive more than one addend per launch
+      BQ_REQUIRE(!det || f32 || epilogue == EPI_BIAS_CE || !s.colsum, BQ_EINVAL,
+                 "bq_gemm_bf16: BQ_GEMM_DET: column sums of a bf16 output are float atomics (use bq_colsum_grouped_det_bf16)");
+      BQ_REQUIRE(!det || epilogue == EPI_BIAS_CE || s.ksplit <= 1 || (!s.colsum && !s.accum && s.o_rpb == 0), BQ_EINVAL,
+                 "bq_gemm_bf16: BQ_GEMM_DET: a cut contraction takes no colsum, accum or output map (problem %d)", done);
       GemmProblem &g = ga.p[ga.n];
       g.P = (const __bf16 *)s.P; g.Q = (const __bf16 *)s.Q; g.out = s.out; g.bias = s.bias; g.out2 = s.out2;
       g.aux = (const __bf16 *)s.aux; g.colsum = s.colsum;
@@ -1689,6 +1501,64 @@ extern "C" int bq_colsum_grouped_bf16(const bq_colsum_desc *d, int n, void *stre
     if (rc) return rc;
   }
   return 0;
+}
+
+// the deterministic forms of the grouped column sums (bq_colsum_grouped_det_bf16) and the fold of a cut contraction
+static long colsum_det_wgs(const bq_colsum_desc *d, int n) {
+  long wgs = 0;
+  for (int k = 0; k < n; ++k) wgs += (long)((d[k].N + 255) / 256) * ((d[k].M + bq::COLSUM_ROWS - 1) / bq::COLSUM_ROWS);
+  return wgs;
+}
+extern "C" long bq_colsum_grouped_det_floats(const bq_colsum_desc *d, int n) {
+  return (d && n > 0) ? 256L * colsum_det_wgs(d, n) : 0;
+}
+
+extern "C" int bq_colsum_grouped_det_bf16(const bq_colsum_desc *d, int n, float *partial, void *stream) {
+  using namespace bq;
+  BQ_REQUIRE(d != nullptr && n >= 1, BQ_EINVAL, "bq_colsum_grouped_det_bf16: no problems");
+  BQ_REQUIRE(partial != nullptr, BQ_EINVAL, "bq_colsum_grouped_det_bf16: no workspace");
+  hipStream_t st = (hipStream_t)stream;
+  int done = 0;
+  long base = 0;   // floats of the workspace used by earlier launches of this call
+  while (done < n) {
+    ColsumArgs ca;
+    ca.n = 0;
+    int wgs = 0, cbs = 0;
+    while (done < n && ca.n < COLSUM_MAX_PROBLEMS) {
+      const bq_colsum_desc &s = d[done];
+      BQ_REQUIRE(s.g && s.out && s.M > 0 && s.N > 0, BQ_EINVAL, "bq_colsum_grouped_det_bf16: bad problem %d", done);
+      BQ_REQUIRE(s.N % 8 == 0 && s.ld % 8 == 0 && ((uintptr_t)s.g % 16 == 0), BQ_EINVAL,
+                 "bq_colsum_grouped_det_bf16: N and ld must be multiples of 8, g 16-byte aligned");
+      ColsumProblem &c = ca.p[ca.n];
+      c.g = (const __bf16 *)s.g; c.out = s.out; c.M = s.M; c.N = s.N; c.ld = s.ld;
+      c.cblocks = (s.N + 255) / 256;
+      c.wg0 = wgs;
+      wgs += c.cblocks * ((s.M + COLSUM_ROWS - 1) / COLSUM_ROWS);
+      cbs += c.cblocks;
+      ++ca.n;
+      ++done;
+    }
+    hipLaunchKernelGGL(colsum_grouped_det_kernel, dim3(wgs), dim3(256), 0, st, ca, partial + base);
+    hipLaunchKernelGGL(colsum_grouped_fold_det_kernel, dim3(cbs), dim3(256), 0, st, ca, (const float *)(partial + base));
+    int rc = check_launch("colsum_grouped_det");
+    if (rc) return rc;
+    base += 256L * wgs;
+  }
+  return 0;
+}
+
+extern "C" int bq_gemm_splitk_fold_det(const float *slab, float *out, void *out_bf16, int pieces, int rows, int cols, int ld,
+                                       void *stream) {
+  using namespace bq;
+  BQ_REQUIRE(slab && (out || out_bf16) && pieces >= 1 && rows >= 0 && cols > 0 && cols % 4 == 0 && ld >= cols && ld % 4 == 0,
+             BQ_EINVAL, "bq_gemm_splitk_fold_det: bad arguments");
+  BQ_REQUIRE((((uintptr_t)slab | (uintptr_t)out) & 15) == 0 && ((uintptr_t)out_bf16 & 7) == 0, BQ_EINVAL,
+             "bq_gemm_splitk_fold_det: unaligned pointer");
+  const long n4 = (long)rows * (cols / 4);
+  if (n4 == 0) return BQ_OK;
+  hipLaunchKernelGGL(splitk_fold_det_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, slab, out,
+                     (__bf16 *)out_bf16, pieces, rows, cols, ld);
+  return check_launch("gemm_splitk_fold_det");
 }
 
 // ======================================================================================================================

@@ -155,6 +155,9 @@ __global__ __launch_bounds__(256) void drop_add_ln_fwd_kernel(const __bf16 *__re
 // reduction over the 4 waves and one atomicAdd per column per workgroup at the end into dgb (2, H), which the
 // FORWARD launch of the same site zeroed (zero_out).  (A last-workgroup fold behind a release fence was measured
 // 8x slower here: the fence has to write back the dx / dresidual lines this kernel just dirtied in L2.)
+// DET (drop_add_ln_bwd_kernel_det, the deterministic training mode): dgb is a slab of (gridDim.x, groups, 2, H) floats and every
+// workgroup STORES its partial row there; ln_dgb_fold_det_kernel adds the rows onto the real accumulator in workgroup order as a
+// second launch (stream order makes the slab visible: no fence, see above).
 template <int NCH>
 __global__ __launch_bounds__(256) void drop_add_ln_bwd_kernel(const __bf16 *__restrict__ x,
                                                               const __bf16 *__restrict__ res,
@@ -165,103 +168,43 @@ __global__ __launch_bounds__(256) void drop_add_ln_bwd_kernel(const __bf16 *__re
                                                               const float *__restrict__ rstd_in,
                                                               __bf16 *__restrict__ dx, __bf16 *__restrict__ dres,
                                                               float *__restrict__ dgb, LnArgs a) {
-  __shared__ float s_g[4][256 * NCH], s_b[4][256 * NCH];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int grp = blockIdx.y, Mg = a.M / a.groups;
-  if (grp) { gamma = a.gamma2; dgb += 2 * a.H; }
-  const unsigned seed = ln_seed(a);
-  float ag[4 * NCH], ab[4 * NCH], gm[4 * NCH];
+  constexpr bool DET = false;
+#include "ln_bwd_kernel_body.h"
+}
+template <int NCH>
+__global__ __launch_bounds__(256) void drop_add_ln_bwd_kernel_det(const __bf16 *__restrict__ x,
+                                                                  const __bf16 *__restrict__ res,
+                                                                  const float *__restrict__ gamma,
+                                                                  const __bf16 *__restrict__ dy,
+                                                                  const __bf16 *__restrict__ dsum,
+                                                                  const float *__restrict__ mean_in,
+                                                                  const float *__restrict__ rstd_in,
+                                                                  __bf16 *__restrict__ dx, __bf16 *__restrict__ dres,
+                                                                  float *__restrict__ dgb, LnArgs a) {
+  constexpr bool DET = true;
+#include "ln_bwd_kernel_body.h"
+}
+
+// dgb[c] += the sum of the `chunks` rows of slab (the LayerNorm backward's (groups, 2, H) accumulators: a few thousand columns,
+// <= 384 rows) in a fixed order -- colsum_fold_kernel's: 64 columns x 4 row phases per workgroup, 8 loads in flight per thread
+__global__ __launch_bounds__(256) void ln_dgb_fold_det_kernel(const float *__restrict__ slab, float *dgb, int chunks, int N) {
+  __shared__ float s[4][64];
+  const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  float t[8];
 #pragma unroll
-  for (int ch = 0; ch < NCH; ++ch) {
-    const float4 g = *reinterpret_cast<const float4 *>(gamma + ch * 256 + lane * 4);
-    gm[ch * 4 + 0] = g.x; gm[ch * 4 + 1] = g.y; gm[ch * 4 + 2] = g.z; gm[ch * 4 + 3] = g.w;
+  for (int u = 0; u < 8; ++u) t[u] = 0.f;
+  if (c < N) {
+    int y = ph;
+    for (; y + 28 < chunks; y += 32) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[u] += slab[(long)(y + 4 * u) * N + c];
+    }
+    for (; y < chunks; y += 4) t[0] += slab[(long)y * N + c];
   }
-#pragma unroll
-  for (int i = 0; i < 4 * NCH; ++i) { ag[i] = 0.0f; ab[i] = 0.0f; }
-  const float invH = 1.0f / (float)a.H;
-  // the loads of row r + stride are issued BEFORE row r is reduced (a wave otherwise has one row = 6 KB in flight and
-  // waits a full memory round trip per row: 2.5 TB/s at the ViT shape)
-  struct Raw {
-    bf16x4 x[NCH], r[NCH], d[NCH], s[NCH];
-    float mean, rstd;
-  };
-  const bf16x4 zero4 = {(__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};
-  auto fetch = [&](int row, Raw &w) {
-    const long rowoff = (long)row * a.H;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int c0 = ch * 256 + lane * 4;
-      w.x[ch] = *reinterpret_cast<const bf16x4 *>(x + rowoff + c0);
-      w.r[ch] = res ? *reinterpret_cast<const bf16x4 *>(res + rowoff + c0) : zero4;
-      w.d[ch] = *reinterpret_cast<const bf16x4 *>(dy + rowoff + c0);
-      w.s[ch] = dsum ? *reinterpret_cast<const bf16x4 *>(dsum + rowoff + c0) : zero4;
-    }
-    w.mean = mean_in[row];
-    w.rstd = rstd_in[row];
-  };
-  const int row_end = (grp + 1) * Mg, stride = gridDim.x * 4;
-  int row = grp * Mg + blockIdx.x * 4 + wid;
-  Raw cur, nxt;
-  if (row < row_end) fetch(row, cur);
-  for (; row < row_end; row += stride) {
-    const bool more = row + stride < row_end;  // wave-uniform
-    if (more) fetch(row + stride, nxt);
-    const long rowoff = (long)row * a.H;
-    float z[4 * NCH], g[4 * NCH];
-    const float ps = ln_path_scale(a, seed, row);
-    const float mean = cur.mean, rstd = cur.rstd;
-    float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int c0 = ch * 256 + lane * 4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = ch * 4 + j;
-        float v = (float)cur.x[ch][j];
-        if (a.thresh) v = ln_keep(seed, row, c0 + j, a.thresh) ? v * a.inv_keep : 0.0f;
-        z[i] = a.x_is_sum ? v : v * ps + (float)cur.r[ch][j];   // dropout(x) * path + residual, as load_z (or the stored sum)
-        const float dyv = (float)cur.d[ch][j];
-        z[i] = (z[i] - mean) * rstd;  // z_hat
-        g[i] = dyv * gm[i];
-        s1 += g[i];
-        s2 += g[i] * z[i];
-        ag[i] += dyv * z[i];
-        ab[i] += dyv;
-      }
-    }
-    s1 = wave_sum_f32(s1) * invH;
-    s2 = wave_sum_f32(s2) * invH;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int c0 = ch * 256 + lane * 4;
-      bf16x4 ox, orr;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = ch * 4 + j;
-        const float dz = rstd * (g[i] - s1 - z[i] * s2) + (float)cur.s[ch][j];
-        orr[j] = (__bf16)dz;
-        float dxv = dz * ps;
-        if (a.thresh) dxv = ln_keep(seed, row, c0 + j, a.thresh) ? dxv * a.inv_keep : 0.0f;
-        ox[j] = (__bf16)dxv;
-      }
-      *reinterpret_cast<bf16x4 *>(dx + rowoff + c0) = ox;
-      if (dres) *reinterpret_cast<bf16x4 *>(dres + rowoff + c0) = orr;
-    }
-    if (more) cur = nxt;
-  }
-#pragma unroll
-  for (int ch = 0; ch < NCH; ++ch)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s_g[wid][ch * 256 + lane * 4 + j] = ag[ch * 4 + j];
-      s_b[wid][ch * 256 + lane * 4 + j] = ab[ch * 4 + j];
-    }
+  s[ph][cl] = ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
   __syncthreads();
-  constexpr int H = 256 * NCH;
-  for (int c = threadIdx.x; c < H; c += 256) {
-    atomicAdd(dgb + c, (s_g[0][c] + s_g[1][c]) + (s_g[2][c] + s_g[3][c]));
-    atomicAdd(dgb + H + c, (s_b[0][c] + s_b[1][c]) + (s_b[2][c] + s_b[3][c]));
-  }
+  if (ph == 0 && c < N) dgb[c] = dgb[c] + ((s[0][cl] + s[1][cl]) + (s[2][cl] + s[3][cl]));
 }
 
 // Column sums of a bf16 (M, N) matrix into f32 (N): the bias gradient of every linear layer (db = sum_rows dY).
@@ -523,10 +466,17 @@ extern "C" __attribute__((visibility("default"))) int bq_twin_drop_add_ln_fwd(
 // dgb: f32 (2, H) = dgamma then dbeta, ACCUMULATED into (float atomics): it must hold zeros on entry -- the
 // forward's zero_out does that.  dx, dresidual bf16 (M, H).  residual / dresidual NULL together for the plain
 // form; dsum (bf16 (M, H), may be NULL) is the gradient that reached sum_out and is added to both.
+// slab != NULL: the deterministic form (bq_drop_add_ln_bwd_det)
+static int ln_bwd_blocks(int M, int groups) {
+  constexpr int bwd_cap = 384;
+  const int blocks = (M / groups + 3) / 4;
+  return blocks > bwd_cap ? bwd_cap : blocks;
+}
 static int ln_bwd_launch(const void *x, const void *residual, const float *gamma, const float *gamma2, int groups,
                          const void *dy, const void *dsum, const float *mean, const float *rstd, void *dx,
                          void *dresidual, float *dgb, int M, int H, float eps, float p_drop, float p_path,
-                         int rows_per_sample, unsigned seed, const unsigned *seed_ptr, void *stream, int x_is_sum = 0) {
+                         int rows_per_sample, unsigned seed, const unsigned *seed_ptr, void *stream, int x_is_sum = 0,
+                         float *slab = nullptr) {
   BQ_REQUIRE(M >= 0 && H > 0 && H % 256 == 0 && H <= 1024, BQ_ELIMIT, "drop_add_ln: H=%d unsupported", H);
   BQ_REQUIRE(groups == 1 || (groups == 2 && gamma2 && M % 2 == 0), BQ_EINVAL, "drop_add_ln_bwd: bad row groups");
   if (M == 0) return BQ_OK;
@@ -538,17 +488,44 @@ static int ln_bwd_launch(const void *x, const void *residual, const float *gamma
            (unsigned)((double)p_path * 4294967296.0), 1.0f / (1.0f - p_path), rows_per_sample, groups, gamma2, nullptr, x_is_sum};
   // (with the cross-row prefetch: 256 / 384 / 512 / 640 / 1024 / 2048 workgroups -> 33.1 / 32.2 / 35.2 / 40.6 / 41.6 / 60.6 us
   // at the ViT shape, tools/bench_ln.py: every workgroup ends with 2 H float atomics on the same 2 H addresses)
-  constexpr int bwd_cap = 384;
-  int blocks = (M / groups + 3) / 4;
-  if (blocks > bwd_cap) blocks = bwd_cap;
+  const int blocks = ln_bwd_blocks(M, groups);
   hipStream_t st = (hipStream_t)stream;
-#define BQ_LN_BWD(N)                                                                                            \
-  hipLaunchKernelGGL(drop_add_ln_bwd_kernel<N>, dim3(blocks, groups), dim3(256), 0, st, (const __bf16 *)x,       \
+#define BQ_LN_BWD(K, N)                                                                                         \
+  hipLaunchKernelGGL(K<N>, dim3(blocks, groups), dim3(256), 0, st, (const __bf16 *)x,                            \
                      (const __bf16 *)residual, gamma, (const __bf16 *)dy, (const __bf16 *)dsum, mean, rstd,      \
-                     (__bf16 *)dx, (__bf16 *)dresidual, dgb, a)
-  switch (H / 256) { case 1: BQ_LN_BWD(1); break; case 2: BQ_LN_BWD(2); break; case 3: BQ_LN_BWD(3); break; default: BQ_LN_BWD(4); }
+                     (__bf16 *)dx, (__bf16 *)dresidual, slab ? slab : dgb, a)
+  if (slab) {
+    switch (H / 256) {
+      case 1: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 1); break;
+      case 2: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 2); break;
+      case 3: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 3); break;
+      default: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 4);
+    }
+    const int N = groups * 2 * H;
+    hipLaunchKernelGGL(ln_dgb_fold_det_kernel, dim3((N + 63) / 64), dim3(256), 0, st, (const float *)slab, dgb, blocks, N);
+    return check_launch("drop_add_ln_bwd_det");
+  }
+  switch (H / 256) {
+    case 1: BQ_LN_BWD(drop_add_ln_bwd_kernel, 1); break;
+    case 2: BQ_LN_BWD(drop_add_ln_bwd_kernel, 2); break;
+    case 3: BQ_LN_BWD(drop_add_ln_bwd_kernel, 3); break;
+    default: BQ_LN_BWD(drop_add_ln_bwd_kernel, 4);
+  }
 #undef BQ_LN_BWD
   return check_launch("drop_add_ln_bwd");
+}
+extern "C" __attribute__((visibility("default"))) long bq_drop_add_ln_bwd_det_slab_floats(int M, int H, int groups) {
+  if (M <= 0 || H <= 0 || groups < 1) return 0;
+  return (long)ln_bwd_blocks(M, groups) * groups * 2 * H;
+}
+extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd_det(
+    const void *x, const void *residual, const float *gamma, const float *gamma2, int groups, const void *dy, const void *dsum,
+    const float *mean, const float *rstd, void *dx, void *dresidual, float *dgb, float *slab, int M, int H, float eps,
+    float p_drop, float p_path, int rows_per_sample, unsigned seed, const unsigned *seed_ptr, int x_is_sum, void *stream) {
+  BQ_REQUIRE(slab || M == 0, BQ_EINVAL, "drop_add_ln_bwd_det: no slab");
+  BQ_REQUIRE(groups == 1 || (!x_is_sum && !dsum && p_path == 0.0f), BQ_EINVAL, "drop_add_ln_bwd_det: two row groups take no sum form");
+  return ln_bwd_launch(x, residual, gamma, groups == 2 ? gamma2 : nullptr, groups, dy, dsum, mean, rstd, dx, dresidual, dgb, M, H,
+                       eps, p_drop, p_path, rows_per_sample, seed, seed_ptr, stream, x_is_sum ? 1 : 0, slab);
 }
 extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd(
     const void *x, const void *residual, const float *gamma, const void *dy, const void *dsum, const float *mean,

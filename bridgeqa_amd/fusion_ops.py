@@ -405,6 +405,30 @@ def new_step(device):
     _CALL_SEED[0] = 0
 
 
+def reset_seeds(seed, device=None):
+    """the counters behind every dropout / drop-path mask of the HIP path back to the state a process seeded with `seed` starts
+    in: the step counter of every device (and of `device`, created if it has none yet) filled in place, the call counter 0
+    (bridgeqa_amd.manual_seed)"""
+    v = int(seed) & 0x7FFFFFFF
+    for t in _STEP_SEED.values():
+        t.fill_(v)
+    if device is not None:
+        step_seed(torch.device(device)).fill_(v)
+    _CALL_SEED[0] = 0
+
+
+def set_deterministic(flag):
+    """bridgeqa_amd.set_deterministic"""
+    from . import set_deterministic as _set
+    return _set(flag)
+
+
+def is_deterministic():
+    """bridgeqa_amd.is_deterministic"""
+    from . import is_deterministic as _is
+    return _is()
+
+
 class _MaskedAttention(torch.autograd.Function):
     """softmax(q k^T * scale + key_mask) v with dropout on the probabilities, through csrc/attn.hip;
     q (B,Lq,H,64), k/v (B,Lk,H,64) bf16 (any strides with a contiguous head dim)."""
@@ -927,6 +951,8 @@ class _TwinKVFn(torch.autograd.Function):
                 f = _ext.GEMM_P_XC | _ext.GEMM_Q_XC | _ext.GEMM_OUT_F32
                 _ext.gemm_grouped([dict(P=xa, Q=ga, out=dw, colsum=db)], f, _ext.EPI_NONE,
                                   256 if (B * ga.shape[1] >= _BIG_ROWS and ga.shape[1] >= 64) else 64)
+                # (accum: ONE adder per element onto what the launch above stored on this stream -- bitwise reproducible as
+                # it is, also in the deterministic mode, which runs it with plain loads and stores)
                 _ext.gemm_grouped([dict(P=xb, Q=gb, out=dw, colsum=db, accum=True)], f, _ext.EPI_NONE, 64)
                 n = dw.shape[0] // 2
                 dws += [dw[:n], dw[n:]]
@@ -1415,7 +1441,8 @@ class _LMHeadCE(torch.autograd.Function):
         dl = _ext.lmhead_ce_dlogits(logits, lse, tgt.view(-1), g, V, eps)   # in place: the logits are consumed
         R = B * L
         # dH (R, D) = dlogits (R, Vp) W (V, D): a 30 528-long contraction for a small output -> cut into pieces that
-        # accumulate with fp32 atomics (the rows of W beyond V are out of bounds for the DMA: zeros)
+        # accumulate with fp32 atomics (the rows of W beyond V are out of bounds for the DMA: zeros); in the deterministic
+        # mode each piece stores its own slab and the slabs are summed in piece order (_ext.gemm_grouped)
         dh = torch.zeros(R, D, dtype=torch.float32, device=h2.device)
         tiles = ((D + 63) // 64) * ((R + 31) // 32)
         ksplit = max(1, min(Vp // 64, (768 + tiles - 1) // tiles))

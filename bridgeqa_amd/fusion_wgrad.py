@@ -234,7 +234,9 @@ def flush_deferred_items(items):
         dbs.update(zip(with_b, _ext.colsum_grouped([items[k][0].reshape(-1, items[k][0].shape[-1]) for k in with_b])))
     if second:
         # second row sources: added onto the stored gradient of their primary record (same stream: ordered behind it) by
-        # the small-tile kernel's atomic epilogue -- short contractions (B x 20 text rows)
+        # the small-tile kernel's atomic epilogue -- short contractions (B x 20 text rows).  ONE adder per element onto a value
+        # an earlier launch of the same stream stored: bitwise reproducible as it is (the deterministic mode runs the same sum
+        # with a plain load and store, gemm64_kernel_det)
         probs = []
         for k in second:
             g2, x2, pk = items[k][0], items[k][1], items[k][4]

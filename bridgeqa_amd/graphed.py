@@ -300,7 +300,8 @@ class GraphedRunner(object):
                 if torch.is_tensor(t):
                     sig.append((k, kk, tuple(t.shape), t.dtype, str(t.device)))
         bn = tuple(mod.momentum for mod in self.model.modules() if isinstance(mod, torch.nn.modules.batchnorm._BatchNorm))
-        return tuple(sig) + (bn,)
+        # (the deterministic mode selects other kernels: graphs captured under one mode are never replayed under the other)
+        return tuple(sig) + (bn, ("deterministic", ops.is_deterministic()))
 
     def _copy_inputs(self, data_dict):
         for k in _INPUT_KEYS:

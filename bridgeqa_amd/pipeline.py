@@ -495,7 +495,8 @@ class PhasedTrainStep(object):
         once per epoch) would have no effect under replay, so step() compares this signature and re-captures"""
         if self._bn_modules is None:
             self._bn_modules = [m for m in self.model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
-        return tuple(m.momentum for m in self._bn_modules)
+        # (so is the deterministic mode, which selects other kernels: a change of mode captures again as well)
+        return tuple(m.momentum for m in self._bn_modules) + (("deterministic", ops.is_deterministic()),)
 
     def capture(self, warmup=3, keep_warmup_updates=False, _again=False):
         """`warmup` eager steps on the phase streams (autograd's AccumulateGrad nodes remember the stream they were

@@ -117,6 +117,16 @@ BQ_API int bq_drop_add_ln_bwd_sum(const void *sum, const float *gamma, const voi
                                   const float *rstd, void *dx, void *dresidual, float *dgb, int M, int H, float eps,
                                   float p_path, int rows_per_sample, unsigned seed, const unsigned *seed_ptr, void *stream);
 
+/* ABI 6, the deterministic training mode: bq_drop_add_ln_bwd (groups = 1, x_is_sum = 0), bq_drop_add_ln_bwd_sum (x = the
+ * stored sum, residual NULL, x_is_sum = 1) and bq_twin_drop_add_ln_bwd (groups = 2, gamma2) in one entry, without float atomics:
+ * every workgroup stores its dgamma / dbeta partial to slab (bq_drop_add_ln_bwd_det_slab_floats(M, H, groups) floats of
+ * scratch from the caller) and a second launch adds them onto dgb (f32 (groups, 2, H)) in workgroup order. */
+BQ_API long bq_drop_add_ln_bwd_det_slab_floats(int M, int H, int groups);
+BQ_API int bq_drop_add_ln_bwd_det(const void *x, const void *residual, const float *gamma, const float *gamma2, int groups,
+                                  const void *dy, const void *dsum, const float *mean, const float *rstd, void *dx,
+                                  void *dresidual, float *dgb, float *slab, int M, int H, float eps, float p_drop, float p_path,
+                                  int rows_per_sample, unsigned seed, const unsigned *seed_ptr, int x_is_sum, void *stream);
+
 /* ---- bias gradient: out[n] = sum_m g[m][n], g bf16 (M,N), out f32 (N) (csrc/ln.hip) -------------------------
  * Replaces grad_output.sum(0) of torch's LinearBackward (every nn.Linear of vit.py / med.py).
  * C = bq_colsum_chunks(M) row chunks; C > 1 needs partial (C*N floats) and, for M <= 2048, counter ((N+255)/256
@@ -313,6 +323,12 @@ BQ_API int bq_fuse_point_features(const int *pix, const float *feat, float *out,
                                kernels: a full persistent grid holds every CU's LDS until it ends and the chain's kernels
                                queue behind it (measured: a 7 us projection took 60 us beside the K/V projection of the image
                                tokens) */
+#define BQ_GEMM_DET 16 /* ABI 6, the deterministic training mode: no float atomic receives more than one addend in the launch.
+                         The fp32-output small-tile forms run on a variant without atomics: ksplit > 1 stores piece p of the
+                         contraction into its own slab out + p * Nj * ldo (ksplit * Nj * ldo floats: the caller's workspace,
+                         summed in piece order by bq_gemm_splitk_fold_det; no colsum, accum or output map with it), accum adds
+                         with a plain load and store.  Refused: column sums of a bf16 output (bq_colsum_grouped_det_bf16 takes
+                         them), tile 128 while a stream-K mode is on. */
 #define BQ_GEMM_EPI_NONE 0
 #define BQ_GEMM_EPI_BIAS 1
 #define BQ_GEMM_EPI_BIAS_GELU 2
@@ -380,6 +396,16 @@ typedef struct bq_colsum_desc {
   int M, N, ld;
 } bq_colsum_desc;
 BQ_API int bq_colsum_grouped_bf16(const bq_colsum_desc *problems, int n, void *stream);
+/* ABI 6, the deterministic training mode: the same sums, out[n] += sum_m g[m*ld + n] with every column's row blocks of 512 rows
+ * added in ascending order by a second launch (no float atomics: bitwise reproducible).  partial: bq_colsum_grouped_det_floats()
+ * floats of scratch from the caller. */
+BQ_API long bq_colsum_grouped_det_floats(const bq_colsum_desc *problems, int n);
+BQ_API int bq_colsum_grouped_det_bf16(const bq_colsum_desc *problems, int n, float *partial, void *stream);
+/* ABI 6: the fold of a cut contraction run with BQ_GEMM_DET: out[r][c] += slab_0[r][c] + slab_1[r][c] + ... in piece order
+ * (slab_p = slab + p * rows * ld, fp32, 16-byte aligned; cols % 4 == 0, ld % 4 == 0); out may be NULL (the sum alone);
+ * out_bf16 (bf16, same layout, may be NULL) also receives the result rounded to bf16. */
+BQ_API int bq_gemm_splitk_fold_det(const float *slab, float *out, void *out_bf16, int pieces, int rows, int cols, int ld,
+                                   void *stream);
 
 /* ---- multi-tensor bf16 transpose (csrc/transpose.hip) ----
  * dst_t (K, N) = src_t (N, K)^T for a list of weight operands in ONE launch: the K-contiguous second copy of the text
