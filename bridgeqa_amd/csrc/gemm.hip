@@ -1457,6 +1457,8 @@ extern "C" int bq_gemm_bf16(const bq_gemm_desc *d, int n, int flags, int epilogu
       } else {
         BQ_REQUIRE(s.ksplit <= 1 || (f32 && tile != 256), BQ_EINVAL, "bq_gemm_bf16: ksplit needs fp32 out and tile 64");
         BQ_REQUIRE(s.ksplit <= 65535, BQ_ELIMIT, "bq_gemm_bf16: ksplit = %d > 65535", s.ksplit);
+        // (every piece of a cut contraction runs the whole epilogue: a bias would be added ksplit times)
+        BQ_REQUIRE(s.ksplit <= 1 || epilogue == EPI_NONE, BQ_EINVAL, "bq_gemm_bf16: ksplit needs the NONE epilogue");
         ks_ = (f32 && tile != 256 && s.ksplit > 1) ? s.ksplit : 1;
       }
       BQ_REQUIRE((s.Ni + ti - 1) / ti <= 65535, BQ_ELIMIT, "bq_gemm_bf16: Ni = %d too wide", s.Ni);

@@ -92,7 +92,7 @@ __device__ __forceinline__ int xg(int kc) { return ((kc >> 1) & 1) | (((kc >> 3)
 // is rounded to bf16.  Phi(x) = sigmoid(x * (a1 + a3 x^2 + a5 x^4)) on |x| <= 8 (clamped beyond: Phi is 0 / 1 to fp32
 // there): a minimax fit of the Gaussian CDF, max |Phi - Phi_erf| = 3.1e-5, max |gelu - gelu_erf| = 3.1e-5, and the
 // derivative of the fitted function differs from gelu_erf' by <= 1.2e-4 (fit and error scan: DESIGN.md §4.4) -- two
-// orders of magnitude below the bf16 rounding (2^-9 relative) applied to the result.  8 VALU operations per element
+// orders of magnitude below the bf16 rounding (2^-8 relative) applied to the result.  8 VALU operations per element
 // (one v_exp_f32, one v_rcp_f32) instead of ~20 for an erf polynomial: the epilogue runs with the matrix pipe idle.
 constexpr float GELU_A1 = 1.59525515f, GELU_A3 = 7.38511083e-2f, GELU_A5 = -6.82350683e-4f;
 __device__ __forceinline__ float gauss_cdf(float x, float &x2) {

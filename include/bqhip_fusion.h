@@ -355,7 +355,7 @@ typedef struct bq_gemm_desc {
                             operand may have rows SHORTER than Kc (e.g. 136 elements of a 3+C = 135 channel point row
                             against Kc = 192) when the other operand is zero-padded to Kc -- the tail of a row then reads
                             the head of the next one (finite values times zeros), bounded by this size */
-  int ksplit;            /* > 1 (fp32 out, tile 64): the contraction runs in ksplit pieces accumulated with fp32 atomics
+  int ksplit;            /* > 1 (fp32 out, tile 64 / 32, epilogue NONE: every piece runs the epilogue): the contraction runs in ksplit pieces accumulated with fp32 atomics
                             into `out`, which the caller zero-fills (weight gradients over millions of rows) */
   /* Batched-row maps (ABI 2).  q_rpb > 0: Q's logical row r (a j row, or a CONTRACTION row when Q is contraction-major)
    * is read at element (r / q_rpb) * q_bstride + (r % q_rpb) * ldq -- a (batch, rows, cols) view whose batches are
