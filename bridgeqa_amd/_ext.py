@@ -468,6 +468,89 @@ def attn_bwd(q, k, v, out, lse, grad_out, scale, dq, dk, dv, mask_log2=None, p_d
                                 int(seed) & 0xFFFFFFFF, _p(seed_tensor), int(bool(causal)), _stream()), "attn_bwd")
 
 
+# ---- single-query decode attention over a static cache (csrc/attn_decode.hip) ------------------------------------------------
+_lib.bq_attn_decode_self.argtypes = [_vp] * 5 + [_i] * 4 + [_l] * 9 + [_f, _vp]
+_lib.bq_attn_decode_self.restype = ctypes.c_int
+_lib.bq_attn_decode_cross.argtypes = [_vp] * 5 + [_i] * 4 + [_l] * 7 + [_f, _vp]
+_lib.bq_attn_decode_cross.restype = ctypes.c_int
+DECODE_CHUNK = 32        # keys per online-softmax step of attn_decode_kernel (DEC_CHUNK)
+DECODE_CALLS = [0, 0]    # launches of attn_decode_self / attn_decode_cross so far (tests assert the route taken)
+
+
+def _decode_operand(t, shape, name):
+    if not t.is_cuda:
+        raise RuntimeError("%s: CPU not supported" % name)
+    if t.dtype != torch.bfloat16 or t.dim() != len(shape) or any(w is not None and int(s) != w for s, w in zip(t.shape, shape)):
+        raise RuntimeError("%s must be a bf16 tensor of shape %s" % (name, "x".join("*" if w is None else str(w) for w in shape)))
+    if t.stride(-1) != 1 or any(st % 8 for st in t.stride()[:-1]) or t.data_ptr() % 16:
+        raise RuntimeError("%s must have a contiguous head dim, strides in multiples of 8 and 16-byte alignment" % name)
+
+
+def _decode_out(out, S, H, like):
+    if out is None:
+        return torch.empty(S, 1, H, 64, dtype=torch.bfloat16, device=like.device)
+    if tuple(out.shape) != (S, 1, H, 64) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != like.device:
+        raise RuntimeError("attn_decode: out must be a contiguous bf16 (S, 1, H, 64) tensor on the operands' device")
+    return out
+
+
+def attn_decode_self(qkv, cache, anc, scale, t=0, t_tensor=None, out=None):
+    """one decode step of self-attention over a static cache.  qkv: bf16 (S, 1, 3, H, 64) packed projection of the step's token;
+    cache: bf16 (S, Lmax, 2, H, 64), row [s, t] is WRITTEN with the step's K / V; anc: int32 (Lmax, S) contiguous, position
+    j < t of slot s is cache row anc[j][s]; the position t from t_tensor (int32 device tensor: replayable) or the host value.
+    Returns out (S, 1, H, 64) bf16."""
+    for x, n in ((qkv, "qkv"), (cache, "cache"), (anc, "anc")):
+        if not x.is_cuda:
+            raise RuntimeError("attn_decode_self: %s: CPU not supported" % n)
+    S, H = qkv.shape[0], qkv.shape[3] if qkv.dim() == 5 else -1
+    _decode_operand(qkv, (S, 1, 3, None, 64), "attn_decode_self: qkv")
+    _decode_operand(cache, (S, None, 2, H, 64), "attn_decode_self: cache")
+    Lmax = cache.shape[1]
+    if anc.dtype != torch.int32 or tuple(anc.shape) != (Lmax, S) or not anc.is_contiguous():
+        raise RuntimeError("attn_decode_self: anc must be a contiguous int32 (Lmax, S) tensor")
+    if t_tensor is not None and (not t_tensor.is_cuda or t_tensor.dtype != torch.int32 or t_tensor.numel() != 1):
+        raise RuntimeError("attn_decode_self: t_tensor must be a one-element int32 device tensor")
+    if t_tensor is None and not 0 <= int(t) < Lmax:
+        raise RuntimeError("attn_decode_self: position %d outside the cache (Lmax %d)" % (t, Lmax))
+    _same_device(qkv, cache, anc, *([t_tensor] if t_tensor is not None else []))
+    with torch.cuda.device(qkv.device):
+        out = _decode_out(out, S, H, qkv)
+        DECODE_CALLS[0] += 1
+        _check(_lib.bq_attn_decode_self(_p(qkv), _p(cache), _p(anc), _p(out), _p(t_tensor), int(t), S, H, Lmax,
+                                        qkv.stride(0), qkv.stride(2), qkv.stride(3), cache.stride(0), cache.stride(1),
+                                        cache.stride(2), cache.stride(3), out.stride(0), out.stride(2), float(scale),
+                                        _stream()), "attn_decode_self")
+    return out
+
+
+def attn_decode_cross(q, kv, scale, mask_log2=None, out=None):
+    """one decode step of cross-attention: q bf16 (S, 1, H, 64) view, kv bf16 (S, Lk, 2, H, 64) by strides (a HoistedKV block),
+    mask_log2 from key_mask_log2 ((S, Lkp) f32) or None.  The keys belong to the slot.  Returns out (S, 1, H, 64) bf16."""
+    for x, n in ((q, "q"), (kv, "kv")) + (((mask_log2, "mask_log2"),) if mask_log2 is not None else ()):
+        if not x.is_cuda:
+            raise RuntimeError("attn_decode_cross: %s: CPU not supported" % n)
+    S, H = q.shape[0], q.shape[2] if q.dim() == 4 else -1
+    _decode_operand(q, (S, 1, None, 64), "attn_decode_cross: q")
+    _decode_operand(kv, (S, None, 2, H, 64), "attn_decode_cross: kv")
+    Lk, Lkp = kv.shape[1], 0
+    if mask_log2 is not None:
+        if mask_log2.dtype != torch.float32 or mask_log2.dim() != 2 or mask_log2.shape[0] != S or mask_log2.shape[1] < Lk \
+                or not mask_log2.is_contiguous():
+            raise RuntimeError("attn_decode_cross: mask_log2 must be a contiguous f32 (S, Lkp >= Lk) tensor")
+        Lkp = mask_log2.shape[1]
+    _same_device(q, kv, *([mask_log2] if mask_log2 is not None else []))
+    if S > 0 and Lk == 0:
+        raise RuntimeError("attn_decode_cross: no keys")
+    with torch.cuda.device(q.device):
+        out = _decode_out(out, S, H, q)
+        k, v = kv[:, :, 0], kv[:, :, 1]
+        DECODE_CALLS[1] += 1
+        _check(_lib.bq_attn_decode_cross(_p(q), _p(k), _p(v), _p(out), _p(mask_log2), S, H, Lk, Lkp, q.stride(0), q.stride(2),
+                                         kv.stride(0), kv.stride(1), kv.stride(3), out.stride(0), out.stride(2), float(scale),
+                                         _stream()), "attn_decode_cross")
+    return out
+
+
 class _AttnSide(ctypes.Structure):
     _fields_ = [("Q", _vp), ("K", _vp), ("V", _vp), ("dO", _vp), ("O", _vp), ("out", _vp), ("dK", _vp), ("dV", _vp),
                 ("LSE", _vp), ("DELTA", _vp), ("mask", _vp), ("Lq", _i), ("Lk", _i), ("Lkp", _i),

@@ -1403,6 +1403,82 @@ def attention_q_kv(q, kv, scale, dropout_p=0.0, mask=None, return_probs=False, s
     return (ctx, probs) if return_probs else ctx
 
 
+# ---- beam-search decoding on a static K/V cache (csrc/attn_decode.hip) ----------------------------------------------------------
+# The reference's decode loop grows every layer's cache by torch.cat and reorders all of it with index_select after every
+# step (models/med.py:196-214, :1466-1470).  Here the cache is ONE allocation that stays in place: slot s writes its step-t key /
+# value row into KV[layer, s, t] and an ancestry table says which physical row holds position j of the hypothesis that
+# currently sits in slot s.  Reordering the beams rewrites that table (Lmax x S int32), not the cache.
+
+def reorder_ancestry(anc, t, beam_idx, identity=None):
+    """The table update of one beam reorder, in place; pure torch (CPU tensors too).  anc: int (Lmax, S); t: positions already
+    written (the NEXT step writes row t); beam_idx (S,): new slot s continues the hypothesis of old slot beam_idx[s].
+    anc[:t] = anc[:t][:, beam_idx]; row t, where every slot is about to write its own row, becomes the identity."""
+    if t > 0:
+        anc[:t] = anc[:t].index_select(1, beam_idx)
+    if t < anc.shape[0]:
+        anc[t] = torch.arange(anc.shape[1], dtype=anc.dtype, device=anc.device) if identity is None else identity
+    return anc
+
+
+def gather_history(cache, anc, t):
+    """(S, t, ...) history of every slot read through the ancestry table: what the decode kernel attends over, and what
+    physically reordering the cache with index_select (models/med.py:1466-1470) would have left in rows [0, t)"""
+    j = torch.arange(t, device=cache.device)
+    return cache[anc[:t].long().t(), j[None, :]]
+
+
+class DecodeLayer(object):
+    """what BertSelfAttention needs of a DecodeCache for one layer (the `past_key_value` of the decode route)"""
+    __slots__ = ("cache", "index")
+
+    def __init__(self, cache, index):
+        self.cache, self.index = cache, index
+
+    def self_attention(self, qkv, scale):
+        """qkv (S, 1, 3, H, 64) of the step's token -> context (S, 1, H, 64); writes the step's row of this layer's cache"""
+        from . import _ext
+        c = self.cache
+        return _ext.attn_decode_self(qkv, c.kv[self.index], c.anc, scale, t=c.t, t_tensor=c.pos)
+
+    def cross_attention(self, q, scale):
+        """q (S, 1, H, 64) -> context over this layer's hoisted question keys / values (they belong to the slot)"""
+        from . import _ext
+        c = self.cache
+        return _ext.attn_decode_cross(q, c.cross[self.index], scale, c.cross_mask)
+
+
+class DecodeCache(object):
+    """Static cache of one beam-search decode: kv bf16 (n_layers, S, Lmax, 2, H, 64) in one allocation, the ancestry table anc
+    int32 (Lmax, S), the position as a device counter `pos` (read by the kernels: a captured step replays) mirrored by the host
+    integer `t`, the HoistedKV of the encoder states (every layer's cross-attention K/V, projected ONCE for the whole decode)
+    and the encoder key mask in kernel format.  advance() after every step, reorder(beam_idx) after the beams moved."""
+
+    def __init__(self, n_layers, S, Lmax, heads, device, hoisted=None, cross_mask=None):
+        self.n_layers, self.S, self.Lmax, self.heads = n_layers, S, Lmax, heads
+        self.kv = torch.zeros(n_layers, S, Lmax, 2, heads, 64, dtype=torch.bfloat16, device=device)
+        self.identity = torch.arange(S, dtype=torch.int32, device=device)
+        self.anc = self.identity[None, :].repeat(Lmax, 1)
+        self.pos = torch.zeros(1, dtype=torch.int32, device=device)
+        self.t = 0
+        self.hoisted = hoisted
+        # (kv(i) waits for the side stream the hoisted projections may run on: done here, once, before any step or capture)
+        self.cross = [hoisted.kv(i) for i in range(n_layers)] if hoisted is not None else None
+        self.cross_mask = cross_mask
+
+    def layer(self, i):
+        return DecodeLayer(self, i)
+
+    def advance(self):
+        if self.t + 1 > self.Lmax:
+            raise RuntimeError("DecodeCache: more than Lmax = %d steps" % self.Lmax)
+        self.t += 1
+        self.pos.add_(1)
+
+    def reorder(self, beam_idx):
+        reorder_ancestry(self.anc, self.t, beam_idx, self.identity)
+        return self
+
+
 class _LMHeadCE(torch.autograd.Function):
     """Tied LM head + shifted label-smoothed cross entropy on the kernels (csrc/gemm.hip cross-entropy epilogue +
     csrc/lmhead.hip): logits computed tile by tile on the MFMA pipeline and stored once as bf16; the loss statistics

@@ -87,8 +87,12 @@ class BertEmbeddings(nn.Module):
         self.position_embedding_type = getattr(config, "position_embedding_type", "absolute")
         self.config = config
 
-    def forward(self, input_ids=None, position_ids=None, inputs_embeds=None, past_key_values_length=0):
+    def forward(self, input_ids=None, position_ids=None, inputs_embeds=None, past_key_values_length=0, decode_cache=None):
+        """decode_cache (extension): an ops.DecodeCache -- the one new token's position is read from its DEVICE counter
+        (index_select, not a Python slice), so that a captured decode step can be replayed at the next position"""
         seq_length = input_ids.size(1) if input_ids is not None else inputs_embeds.size(1)
+        if decode_cache is not None:
+            position_ids = self.position_ids.index_select(1, decode_cache.pos)
         if position_ids is None:
             position_ids = self.position_ids[:, past_key_values_length:seq_length + past_key_values_length]
         if inputs_embeds is None:
@@ -153,6 +157,19 @@ class BertSelfAttention(nn.Module):
         # the fused kernels also serve output_attentions (the map is rebuilt from the LSE, detached); a caller that
         # differentiates through the map -- save_attention + the attn_gradients hook -- gets the reference composition
         hooked = is_cross and self.save_attention
+        if isinstance(past_key_value, ops.DecodeLayer):
+            # beam-search decoding on the static cache (generate, _DECODE_CACHE): one new token per slot; the kernel appends
+            # the step's K / V row in place and reads the hypothesis' history through the ancestry table
+            if hooked or output_attentions or not (hoisted_kv or not is_cross) or hidden_states.shape[1] != 1:
+                raise RuntimeError("the decode cache serves one new token per slot, hoisted encoder states, no attention maps")
+            S = hidden_states.shape[0]
+            if is_cross:
+                q = self._heads(ops.linear(hidden_states, self.query.weight, self.query.bias))
+                ctx = past_key_value.cross_attention(q, 1.0 / math.sqrt(D))
+            else:
+                qkv = ops.multi_linear(hidden_states, (self.query, self.key, self.value)).view(S, 1, 3, H, D)
+                ctx = past_key_value.self_attention(qkv, 1.0 / math.sqrt(D))
+            return (ctx.reshape(S, 1, self.all_head_size), past_key_value)
         if (not hooked and past_key_value is None
                 and ops.compute_dtype() == torch.bfloat16 and (hidden_states.is_cuda or hoisted_kv)):
             # fused projections: Q/K/V (self) or K/V (cross) as ONE GEMM over the shared input, and the attention
@@ -309,7 +326,8 @@ class BertLayer(nn.Module):
     def forward(self, hidden_states, attention_mask=None, head_mask=None, encoder_hidden_states=None,
                 encoder_attention_mask=None, past_key_value=None, output_attentions=False, mode=None,
                 layernorm_idx=0):
-        self_past = past_key_value[:2] if past_key_value is not None else None
+        decode = isinstance(past_key_value, ops.DecodeLayer)   # static decode cache: serves the cross-attention too
+        self_past = past_key_value if decode else (past_key_value[:2] if past_key_value is not None else None)
         self_out = self.attention(hidden_states, attention_mask, head_mask, output_attentions=output_attentions,
                                   past_key_value=self_past)
         attention_output = self_out[0]
@@ -318,7 +336,8 @@ class BertLayer(nn.Module):
         if mode == "multimodal":
             assert encoder_hidden_states is not None, "encoder_hidden_states must be given for cross-attention layers"
             cross_out = self.crossattention(attention_output, attention_mask, head_mask, encoder_hidden_states,
-                                            encoder_attention_mask, output_attentions=output_attentions)
+                                            encoder_attention_mask, past_key_value if decode else None,
+                                            output_attentions=output_attentions)
             attention_output = cross_out[0]
             outputs = outputs + cross_out[1:-1]
         layer_output = self.feed_forward_chunk(attention_output, layernorm_idx)
@@ -331,6 +350,13 @@ class BertLayer(nn.Module):
 
 
 _TWIN_BATCH = [True]  # both text streams of a twin level as one stacked batch
+# generate on the static K/V cache + the fused decode-attention kernel (ops.DecodeCache, csrc/attn_decode.hip) whenever the
+# decode is eligible (BertLMHeadModel.decode_session); BQ_DECODE_CACHE=0: the growing torch.cat cache of the reference
+_DECODE_CACHE = [os.environ.get("BQ_DECODE_CACHE", "1") != "0"]
+# ... with the second step captured and replayed for the rest of the decode (3.7x against 1.45x for the eager cache route at the
+# reference's shape, profiles/generate_decode.md: the default since it won at both question lengths); BQ_DECODE_GRAPH=0: eager
+_DECODE_GRAPH = [os.environ.get("BQ_DECODE_GRAPH", "1") != "0"]
+_DECODE_STATS = {"sessions": 0, "captures": 0}   # decode sessions opened / steps captured so far (tests)
 _HOIST_CROSS_KV = True  # plain encoder / decoder: all layers' cross K/V in one GEMM
 
 
@@ -355,8 +381,15 @@ class BertEncoder(nn.Module):
         next_decoder_cache = () if use_cache else None
         layers = [i for i in range(self.config.num_hidden_layers) if forward_layers is None or i in forward_layers]
         hoisted = None
+        decode = past_key_values if isinstance(past_key_values, ops.DecodeCache) else None
+        if decode is not None:
+            # the cache carries the cross-attention K/V of the unchanged encoder states, projected once for the whole decode
+            # (today's cached path skips the hoist below and re-projects them in every layer of every step)
+            if mode != "multimodal" or forward_layers is not None or output_attentions or decode.hoisted is None:
+                raise RuntimeError("the decode cache serves the whole multimodal decoder without attention maps")
+            hoisted = decode.hoisted
         key_only = lambda m: m is None or (m.dim() == 4 and m.shape[1] == 1 and m.shape[2] == 1)
-        if (_HOIST_CROSS_KV and mode == "multimodal" and len(layers) > 1 and past_key_values is None
+        if (decode is None and _HOIST_CROSS_KV and mode == "multimodal" and len(layers) > 1 and past_key_values is None
                 and torch.is_tensor(encoder_hidden_states) and encoder_hidden_states.is_cuda
                 and ops.compute_dtype() == torch.bfloat16 and key_only(encoder_attention_mask)
                 and self.layer[0].crossattention.self.attention_head_size == 64
@@ -370,7 +403,10 @@ class BertEncoder(nn.Module):
         for n, i in enumerate(layers):
             if output_hidden_states:
                 all_hidden_states = all_hidden_states + (hidden_states,)
-            past_key_value = past_key_values[i] if past_key_values is not None else None
+            if decode is not None:
+                past_key_value = decode.layer(i)
+            else:
+                past_key_value = past_key_values[i] if past_key_values is not None else None
             want = _wants(output_attentions, i, layers[-1])
             layer_outputs = self.layer[i](hidden_states, attention_mask, None,
                                           HoistedStates(hoisted, n) if hoisted is not None else encoder_hidden_states,
@@ -385,7 +421,9 @@ class BertEncoder(nn.Module):
                     all_cross_attentions = all_cross_attentions + (layer_outputs[2],)
         if output_hidden_states:
             all_hidden_states = all_hidden_states + (hidden_states,)
-        if hoisted is not None:
+        if decode is not None:
+            next_decoder_cache = decode
+        elif hoisted is not None:
             # (HoistedKV -> its outputs -> their autograd node -> ctx.hold -> HoistedKV is a reference cycle through C++
             # autograd nodes that Python's collector cannot see: the whole autograd graph of a forward -- and the
             # AccumulateGrad nodes of every parameter under it -- stayed alive after its outputs were dropped)
@@ -717,6 +755,16 @@ class BertModel(BertPreTrainedModel):
         output_hidden_states = output_hidden_states if output_hidden_states is not None \
             else self.config.output_hidden_states
         use_cache = (use_cache if use_cache is not None else self.config.use_cache) if is_decoder else False
+        if isinstance(past_key_values, ops.DecodeCache):
+            # one decode step on the static cache: every slot sees all of its own history (the all-ones mask of
+            # prepare_inputs_for_generation) and the encoder mask is in the cache, converted once -- no mask is built per step
+            if input_ids is None or input_ids.shape[1] != 1 or not is_decoder:
+                raise RuntimeError("the decode cache takes one new token id per slot of a decoder")
+            emb = self.embeddings(input_ids=input_ids, decode_cache=past_key_values)
+            enc = self.encoder(emb, past_key_values=past_key_values, use_cache=True, mode=mode, layernorm_idx=layernorm_idx)
+            return ModelOutput(last_hidden_state=enc.last_hidden_state, pooler_output=None,
+                               past_key_values=enc.past_key_values, hidden_states=None, attentions=None,
+                               cross_attentions=None)
         attention_mask, ext_mask, past_len = self._prep(input_ids, inputs_embeds, encoder_embeds, attention_mask,
                                                         past_key_values, is_decoder, mask_prep)
         enc_ext = None
@@ -800,6 +848,48 @@ class BertModelTwin(BertModel):
                            attentions=enc.attentions, cross_attentions=enc.cross_attentions)
 
 
+class DecodeSession(object):
+    """One beam-search decode of a BertLMHeadModel on an ops.DecodeCache: step(ids (S, 1)) -> logits (S, V) of the new
+    position, reorder(beam_idx) after the beams moved.  graph=True (generate's default, _DECODE_GRAPH): the first step runs
+    eagerly (it also warms every kernel and operand cache up), the second is captured -- embeddings -> layers -> LM-head logits on ONE stream, no fork, reading
+    the token ids from a static buffer and the position from the cache's device counter -- and replayed from then on; the
+    logits it returns are then a STATIC buffer the next step overwrites.  Top-k, beam bookkeeping and reorder stay outside."""
+
+    def __init__(self, model, cache, graph=False):
+        self.model, self.cache, self.use_graph = model, cache, bool(graph)
+        self.graph = self.ids = self.logits = None
+        _DECODE_STATS["sessions"] += 1
+
+    def _forward(self, ids):
+        out = self.model(input_ids=ids, past_key_values=self.cache, use_cache=True, is_decoder=True, return_dict=True)
+        return out.logits[:, -1, :]
+
+    @torch.no_grad()
+    def step(self, ids):
+        c = self.cache
+        if c.t >= c.Lmax:
+            raise RuntimeError("DecodeSession: the cache holds %d positions" % c.Lmax)
+        if not self.use_graph or c.t == 0:
+            logits = self._forward(ids)
+        else:
+            if self.graph is None:
+                self.ids = ids.clone(memory_format=torch.contiguous_format)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self.logits = self._forward(self.ids)
+                _DECODE_STATS["captures"] += 1
+            else:
+                self.ids.copy_(ids)
+            self.graph.replay()
+            logits = self.logits
+        c.advance()
+        return logits
+
+    def reorder(self, beam_idx):
+        self.cache.reorder(beam_idx)
+        return self
+
+
 class BertLMHeadModel(BertPreTrainedModel):
     """Causal answer decoder with the LM head tied to the word embeddings; label-smoothed CE."""
 
@@ -867,8 +957,42 @@ class BertLMHeadModel(BertPreTrainedModel):
         return tuple(tuple(t.index_select(0, beam_idx) for t in layer_past) for layer_past in past)
 
     @torch.no_grad()
+    def decode_session(self, input_ids, max_length, encoder_hidden_states=None, encoder_attention_mask=None, graph=None):
+        """A DecodeSession for decoding from the one-token prompts input_ids (S, 1) (S = batch * beams slots; the states /
+        mask already have S rows) up to max_length tokens, or None when the decode is not eligible for the static cache --
+        everything is checked HERE, before the first step; there is no fallback in the middle of a decode.  Eligible: the
+        switch on, bf16 compute dtype, CUDA tensors, head size 64, a prompt of one token, encoder states given as a tensor
+        with a (S, Lenc) key mask (or none), no save_attention hook, fp32 nn.Parameter weights with biases in every attention
+        projection.  The hoisted cross K/V projections of all layers and the encoder mask conversion run now, once."""
+        enc, em = encoder_hidden_states, encoder_attention_mask
+        layers = list(self.bert.encoder.layer)
+        cfg = self.config
+        if not (_DECODE_CACHE[0] and ops.compute_dtype() == torch.bfloat16 and input_ids.is_cuda and input_ids.dim() == 2
+                and input_ids.shape[1] == 1 and torch.is_tensor(enc) and enc.is_cuda and enc.dim() == 3
+                and enc.shape[0] == input_ids.shape[0] and enc.shape[1] > 0
+                and (em is None or (torch.is_tensor(em) and em.is_cuda and tuple(em.shape) == tuple(enc.shape[:2])))
+                and cfg.hidden_size // cfg.num_attention_heads == 64 and max_length <= cfg.max_position_embeddings
+                and all(hasattr(l, "crossattention") for l in layers)):
+            return None
+        for l in layers:
+            sa, ca = l.attention.self, l.crossattention.self
+            if sa.save_attention or ca.save_attention:
+                return None
+            for lin in (sa.query, sa.key, sa.value, ca.query, ca.key, ca.value):
+                if lin.bias is None or not ops._param_ok(lin.weight, lin.bias):
+                    return None
+        S, H = input_ids.shape[0], cfg.num_attention_heads
+        from . import _ext
+        hoisted = ops.HoistedKV(ops._c(enc), [l.crossattention.self for l in layers], H)
+        mask = None
+        if em is not None:
+            mask = _ext.key_mask_log2(self.invert_attention_mask(em), S, enc.shape[1])
+        cache = ops.DecodeCache(len(layers), S, max_length, H, enc.device, hoisted, mask)
+        return DecodeSession(self, cache, _DECODE_GRAPH[0] if graph is None else graph)
+
+    @torch.no_grad()
     def generate(self, input_ids, max_length=20, min_length=0, num_beams=1, eos_token_id=None, pad_token_id=None,
-                 length_penalty=1.0, early_stopping=False, return_scores=False, **model_kwargs):
+                 length_penalty=1.0, early_stopping=False, return_scores=False, graph=None, **model_kwargs):
         """beam search as `transformers` v4.15 `generate` runs it for a decoder-only model (generation.py; parity
         unpinned): input_ids (B, L0) is repeated num_beams times per sample; encoder_hidden_states / encoder_attention_mask
         must already have B * num_beams rows (the caller chooses what every beam slot attends to)."""
@@ -879,6 +1003,17 @@ class BertLMHeadModel(BertPreTrainedModel):
         enc = model_kwargs.get("encoder_hidden_states")
         if enc is not None and enc.shape[0] != ids.shape[0]:
             raise ValueError("encoder_hidden_states must have batch * num_beams = %d rows, got %d" % (ids.shape[0], enc.shape[0]))
+
+        # eligible decodes run on a static K/V cache (decode_session): step / reorder below do underneath beam_search what the
+        # two closures after them do by growing and index_select-ing the reference's cache; graph: replay one captured step
+        # (None: BQ_DECODE_GRAPH)
+        session = self.decode_session(ids, max_length, enc, model_kwargs.get("encoder_attention_mask"), graph=graph)
+        if session is not None:
+            seq, scores = beam_search(lambda cur, past: (session.step(cur[:, -1:]), session),
+                                      lambda past, beam_idx: past.reorder(beam_idx), ids, num_beams, max_length,
+                                      eos_token_id, pad_token_id, min_length=min_length, length_penalty=length_penalty,
+                                      early_stopping=early_stopping)
+            return (seq, scores) if return_scores else seq
 
         def step(cur, past):
             inp = self.prepare_inputs_for_generation(cur, past=past, **model_kwargs)

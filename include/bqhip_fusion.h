@@ -90,6 +90,26 @@ BQ_API int bq_attn_bwd2(const void *Q, const void *K, const void *V, const void 
                         long g_rs, long g_hs, float scale, float p_drop, unsigned seed, const unsigned *seed_ptr,
                         void *stream);
 
+/* ---- single-query attention of beam-search decoding over a static cache (csrc/attn_decode.hip; additive to ABI 6) ----
+ * Replaces, from the second generated token on, the past_key_value branch of models/med.py:179-217 as HF's GenerationMixin
+ * drives it (key_layer = cat(past, key), ... per layer and step) and the per-step index_select of every cached tensor
+ * (models/med.py:1466-1470 _reorder_cache): one query row per (slot, head), head dim 64, bf16 operands, fp32 scores and
+ * softmax (scale * log2 e folded in, exp2), bf16 output; any number of keys (chunks of 32, online softmax); no atomics.
+ * bq_attn_decode_self: qkv (S, 1, 3, H, 64) the step's packed projection by strides q_bs / q_ks / q_hs (slot, q-k-v axis, head);
+ *   kv_cache (S, Lmax, 2, H, 64) by strides c_bs / c_rs / c_ks / c_hs; anc int32 (Lmax, S) contiguous: position j < t of slot
+ *   s is cache row anc[j][s]; position t = *t_ptr (device int32; NULL: the host value t).  The launch stores the step's K / V
+ *   row into kv_cache[s, t] (and nothing else in the cache), attends over positions 0 .. t (position t from registers) and
+ *   writes O (S, 1, H, 64) by strides o_bs / o_hs.  Ancestry rows and t are clamped into the cache.
+ * bq_attn_decode_cross: Q (S, 1, H, 64), K / V (S, Lk, H, 64) by strides as in bq_attn_fwd (a hoisted (S, Lk, 2, H, 64) block);
+ *   mask NULL or f32 (S, Lkp) additive key mask times log2(e), Lkp >= Lk.  The keys belong to the SLOT: no ancestry.
+ * All strides in elements and multiples of 8, pointers 16-byte aligned.  S == 0: no-op. */
+BQ_API int bq_attn_decode_self(const void *qkv, void *kv_cache, const int32_t *anc, void *O, const int *t_ptr, int t, int S,
+                               int H, int Lmax, long q_bs, long q_ks, long q_hs, long c_bs, long c_rs, long c_ks, long c_hs,
+                               long o_bs, long o_hs, float scale, void *stream);
+BQ_API int bq_attn_decode_cross(const void *Q, const void *K, const void *V, void *O, const float *mask, int S, int H, int Lk,
+                                int Lkp, long q_bs, long q_hs, long k_bs, long k_rs, long k_hs, long o_bs, long o_hs,
+                                float scale, void *stream);
+
 /* ---- y = LayerNorm(path(dropout(x)) + residual) (csrc/ln.hip) -----------------------------------------------
  * Replaces  hidden = dense(x); hidden = dropout(hidden); hidden = LayerNorm(hidden + input)
  *   models/med.py:236-239 (BertSelfOutput), :313-317 (BertOutput)   [residual != NULL, p_drop]
