@@ -551,6 +551,87 @@ def attn_decode_cross(q, kv, scale, mask_log2=None, out=None):
     return out
 
 
+# ---- attention of answer ranking: candidate sequences sharing their question's K / V (csrc/attn_rank.hip) -------------------------
+_lib.bq_attn_rank_self.argtypes = [_vp] * 3 + [_i] * 4 + [_l] * 7 + [_f, _vp]
+_lib.bq_attn_rank_self.restype = ctypes.c_int
+_lib.bq_attn_rank_cross.argtypes = [_vp] * 5 + [_i] * 7 + [_l] * 9 + [_f, _vp]
+_lib.bq_attn_rank_cross.restype = ctypes.c_int
+RANK_LMAX = 32         # tokens per sequence attn_rank_self holds in registers (BQ_RANK_LMAX)
+RANK_QBLOCK = 4        # queries a wave of attn_rank_cross carries through one loaded K / V chunk (BQ_RANK_QBLOCK)
+RANK_CALLS = [0, 0]    # launches of attn_rank_self / attn_rank_cross that the library accepted (tests assert the route taken)
+# (contract of both wrappers, relied on by tests/test_attn_rank_cpu.py: between the is_cuda checks and the last operand check
+# nothing touches the device -- only shape, dtype, stride and data_ptr are read)
+
+
+def _rank_mask(mask_log2, rows, keys, name, what):
+    if mask_log2 is None:
+        return 0
+    if mask_log2.dtype != torch.float32 or mask_log2.dim() != 2 or mask_log2.shape[0] != rows or mask_log2.shape[1] < keys \
+            or not mask_log2.is_contiguous():
+        raise RuntimeError("%s: mask_log2 must be a contiguous f32 %s tensor" % (name, what))
+    return mask_log2.shape[1]
+
+
+def _rank_out(out, N, La, H, like, name):
+    if out is None:
+        return torch.empty(N, La, H, 64, dtype=torch.bfloat16, device=like.device)
+    if tuple(out.shape) != (N, La, H, 64) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != like.device:
+        raise RuntimeError("%s: out must be a contiguous bf16 (N, La, H, 64) tensor on the operands' device" % name)
+    return out
+
+
+def attn_rank_self(qkv, scale, mask_log2=None, out=None):
+    """causal self-attention of N short sequences on their packed projection.  qkv: bf16 (N, La, 3, H, 64) by strides (as
+    multi_linear writes it), La <= RANK_LMAX; mask_log2 from key_mask_log2 ((N, Lap >= La) f32, finite) or None: query i sees
+    key j iff j <= i, the key mask on top.  Returns out (N, La, H, 64) bf16."""
+    for x, n in ((qkv, "qkv"),) + (((mask_log2, "mask_log2"),) if mask_log2 is not None else ()):
+        if not x.is_cuda:
+            raise RuntimeError("attn_rank_self: %s: CPU not supported" % n)
+    N, La, H = (qkv.shape[0], qkv.shape[1], qkv.shape[3]) if qkv.dim() == 5 else (-1, -1, -1)
+    _decode_operand(qkv, (N, La, 3, None, 64), "attn_rank_self: qkv")
+    if La > RANK_LMAX:
+        raise RuntimeError("attn_rank_self: %d tokens per sequence, the kernel holds %d" % (La, RANK_LMAX))
+    if N > 0 and La == 0:
+        raise RuntimeError("attn_rank_self: no tokens")
+    Lap = _rank_mask(mask_log2, N, La, "attn_rank_self", "(N, Lap >= La)")
+    _same_device(qkv, *([mask_log2] if mask_log2 is not None else []))
+    with torch.cuda.device(qkv.device):
+        out = _rank_out(out, N, La, H, qkv, "attn_rank_self")
+        _check(_lib.bq_attn_rank_self(_p(qkv), _p(out), _p(mask_log2), N, H, La, Lap, qkv.stride(0), qkv.stride(1),
+                                      qkv.stride(2), qkv.stride(3), out.stride(0), out.stride(1), out.stride(2), float(scale),
+                                      _stream()), "attn_rank_self")
+        RANK_CALLS[0] += 1
+    return out
+
+
+def attn_rank_cross(q, kv, scale, group, mask_log2=None, out=None):
+    """cross-attention of N = Bq * group sequences over the keys / values of their question: q bf16 (N, La, H, 64) view, kv bf16
+    (Bq, Lk, 2, H, 64) by strides (a HoistedKV block over the UNTILED question states), sequence n reads question n // group;
+    mask_log2 from key_mask_log2 ((Bq, Lkp >= Lk) f32) or None.  Returns out (N, La, H, 64) bf16."""
+    for x, n in ((q, "q"), (kv, "kv")) + (((mask_log2, "mask_log2"),) if mask_log2 is not None else ()):
+        if not x.is_cuda:
+            raise RuntimeError("attn_rank_cross: %s: CPU not supported" % n)
+    N, La, H = (q.shape[0], q.shape[1], q.shape[2]) if q.dim() == 4 else (-1, -1, -1)
+    _decode_operand(q, (N, La, None, 64), "attn_rank_cross: q")
+    _decode_operand(kv, (None, None, 2, H, 64), "attn_rank_cross: kv")
+    Bq, Lk = kv.shape[0], kv.shape[1]
+    group = int(group)
+    if group < 1 or Bq * group != N:
+        raise RuntimeError("attn_rank_cross: group %d: %d sequences are not %d questions x group" % (group, N, Bq))
+    Lkp = _rank_mask(mask_log2, Bq, Lk, "attn_rank_cross", "(Bq, Lkp >= Lk)")
+    _same_device(q, kv, *([mask_log2] if mask_log2 is not None else []))
+    if N > 0 and (Lk == 0 or La == 0):
+        raise RuntimeError("attn_rank_cross: no keys or no queries")
+    with torch.cuda.device(q.device):
+        out = _rank_out(out, N, La, H, q, "attn_rank_cross")
+        k, v = kv[:, :, 0], kv[:, :, 1]
+        _check(_lib.bq_attn_rank_cross(_p(q), _p(k), _p(v), _p(out), _p(mask_log2), N, Bq, group, H, La, Lk, Lkp, q.stride(0),
+                                       q.stride(1), q.stride(2), kv.stride(0), kv.stride(1), kv.stride(3), out.stride(0),
+                                       out.stride(1), out.stride(2), float(scale), _stream()), "attn_rank_cross")
+        RANK_CALLS[1] += 1
+    return out
+
+
 class _AttnSide(ctypes.Structure):
     _fields_ = [("Q", _vp), ("K", _vp), ("V", _vp), ("dO", _vp), ("O", _vp), ("out", _vp), ("dK", _vp), ("dV", _vp),
                 ("LSE", _vp), ("DELTA", _vp), ("mask", _vp), ("Lq", _i), ("Lk", _i), ("Lkp", _i),

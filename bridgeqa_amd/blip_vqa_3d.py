@@ -400,6 +400,12 @@ class BLIP_VQA3D(nn.Module):
         text_decoder = self.text_decoder_scene if use_scene else self.text_decoder
         num_ques = question_states.size(0)
         start_ids = answer_ids[0, 0].repeat(num_ques, 1)  # bos token
+        # eligible calls (med.BertLMHeadModel.rank_shared, BQ_RANK_SHARED) project the question states to every layer's K/V
+        # ONCE and both passes read them in place: the first-token pass with one sequence per question, the re-score with k
+        shared = text_decoder.rank_shared(question_states, question_atts, answer_ids, answer_atts,
+                                          min(answer_ids.size(0), k))
+        if shared is not None:
+            question_states, question_atts = shared.grouped(1), None
         start_output = text_decoder(start_ids, encoder_hidden_states=question_states,
                                     encoder_attention_mask=question_atts, return_dict=True, reduction="none")
         logits = start_output.logits[:, 0, :].float()
@@ -410,8 +416,11 @@ class BLIP_VQA3D(nn.Module):
         input_ids = answer_ids[topk_ids.reshape(-1)]   # (num_ques*k, La): question-major, as the reference's loop
         input_atts = answer_atts[topk_ids.reshape(-1)]
         targets_ids = input_ids.masked_fill(input_ids == self.tokenizer.pad_token_id, -100)
-        question_states = tile(question_states, 0, k)
-        question_atts = tile(question_atts, 0, k)
+        if shared is not None:
+            question_states = shared.grouped(k)   # never tiled: sequence n reads question n // k
+        else:
+            question_states = tile(question_states, 0, k)
+            question_atts = tile(question_atts, 0, k)
         output = text_decoder(input_ids, attention_mask=input_atts, encoder_hidden_states=question_states,
                               encoder_attention_mask=question_atts, labels=targets_ids, return_dict=True,
                               reduction="none")

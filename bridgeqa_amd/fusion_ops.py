@@ -1479,6 +1479,65 @@ class DecodeCache(object):
         return self
 
 
+# ---- answer ranking on the shared K/V of the question (csrc/attn_rank.hip) -------------------------------------------------------
+# The reference re-scores k candidate answers per question against question states tiled k times (models/blip_vqa_3d.py:509-566)
+# and every decoder layer projects the tiled rows to K / V.  The K / V of a question do not depend on the candidate: here they
+# are projected ONCE from the untiled (Bq, Lq, 768) states and candidate sequence n reads question n // group.
+
+class RankLayer(object):
+    """what BertSelfAttention needs of a RankShared for one layer: the HoistedStates of the ranking route (`hoisted`, `slot`)
+    plus `group`; handed to the layer as its encoder_hidden_states and to its self-attention as the `rank` argument"""
+    __slots__ = ("shared", "slot")
+
+    def __init__(self, shared, slot):
+        self.shared, self.slot = shared, slot
+
+    @property
+    def hoisted(self):
+        return self.shared.hoisted
+
+    @property
+    def group(self):
+        return self.shared.group
+
+    def self_attention(self, qkv, scale, key_mask):
+        """qkv (N, La, 3, H, 64), key_mask the factored (N, 1, 1, La) additive mask -> causal context (N, La, H, 64)"""
+        from . import _ext
+        return _ext.attn_rank_self(qkv, scale, _mask_log2(key_mask, qkv.shape[0], qkv.shape[1]))
+
+    def cross_attention(self, q, scale):
+        """q (N, La, H, 64) -> context over this layer's keys / values of question n // group"""
+        from . import _ext
+        s = self.shared
+        return _ext.attn_rank_cross(q, s.blocks[self.slot], scale, s.group, s.mask_log2)
+
+
+class RankShared(object):
+    """encoder_hidden_states of the ranking route: ONE HoistedKV over the untiled question states (Bq, Lq, 768) for all decoder
+    layers, the question key mask in kernel format, and `group` -- how many consecutive decoder sequences read each question
+    (1: the first-token pass, k: the re-score).  Built once per rank_answer call (BertLMHeadModel.rank_shared); inference only:
+    there is no backward."""
+
+    def __init__(self, states, selfattns, heads, key_mask=None):
+        from . import _ext
+        self.Bq, self.Lq = int(states.shape[0]), int(states.shape[1])
+        self.hoisted = HoistedKV(_c(states), selfattns, heads)
+        # (kv(i) waits for the side stream the hoisted projections may run on: done here, once)
+        self.blocks = [self.hoisted.kv(i) for i in range(self.hoisted.n)]
+        self.mask_log2 = None if key_mask is None else _ext.key_mask_log2(key_mask, self.Bq, self.Lq)
+        self.group = 1
+
+    def grouped(self, group):
+        """a view of the same projections and mask for `group` consecutive sequences per question (this object is unchanged)"""
+        import copy
+        v = copy.copy(self)
+        v.group = int(group)
+        return v
+
+    def layer(self, i):
+        return RankLayer(self, i)
+
+
 class _LMHeadCE(torch.autograd.Function):
     """Tied LM head + shifted label-smoothed cross entropy on the kernels (csrc/gemm.hip cross-entropy epilogue +
     csrc/lmhead.hip): logits computed tile by tile on the MFMA pipeline and stored once as bf16; the loss statistics

@@ -144,9 +144,10 @@ class BertSelfAttention(nn.Module):
         return x.view(x.shape[0], x.shape[1], self.num_attention_heads, self.attention_head_size)
 
     def forward(self, hidden_states, attention_mask=None, head_mask=None, encoder_hidden_states=None,
-                encoder_attention_mask=None, past_key_value=None, output_attentions=False, tap=None):
+                encoder_attention_mask=None, past_key_value=None, output_attentions=False, tap=None, rank=None):
         """tap: an ops.GradTap -- the projection that reads hidden_states adds the gradient parked there (the residual
-        branch of the following BertSelfOutput) to its input gradient"""
+        branch of the following BertSelfOutput) to its input gradient.  rank: the layer's ops.RankLayer when this is the
+        SELF-attention of the ranking route (its cross-attention gets it as encoder_hidden_states)"""
         if head_mask is not None:
             raise NotImplementedError("head_mask is always None on the BridgeQA path")
         is_cross = encoder_hidden_states is not None
@@ -170,6 +171,26 @@ class BertSelfAttention(nn.Module):
                 qkv = ops.multi_linear(hidden_states, (self.query, self.key, self.value)).view(S, 1, 3, H, D)
                 ctx = past_key_value.self_attention(qkv, 1.0 / math.sqrt(D))
             return (ctx.reshape(S, 1, self.all_head_size), past_key_value)
+        if is_cross and isinstance(encoder_hidden_states, ops.RankLayer):
+            rank = encoder_hidden_states
+        if rank is not None:
+            # answer ranking on the shared K/V of the question (rank_shared, _RANK_SHARED): N = Bq * group candidate sequences,
+            # one wave per (sequence, head); the cross-attention reads the K/V of question n // group, projected once
+            key_mask = None if is_cross else getattr(attention_mask, "_bq_causal_key_mask", None)
+            if (hooked or output_attentions or torch.is_grad_enabled() or past_key_value is not None or p_drop > 0
+                    or not (is_cross or key_mask is not None)):
+                raise RuntimeError("the ranking route serves inference with a factored causal mask and no attention maps")
+            N, La = hidden_states.shape[:2]
+            if is_cross:
+                q = self._heads(ops.linear(hidden_states, self.query.weight, self.query.bias))
+                ctx = rank.cross_attention(q, 1.0 / math.sqrt(D))
+                kv = rank.shared.blocks[rank.slot]
+                present = (kv[:, :, 0].permute(0, 2, 1, 3), kv[:, :, 1].permute(0, 2, 1, 3))
+            else:
+                qkv = ops.multi_linear(hidden_states, (self.query, self.key, self.value)).view(N, La, 3, H, D)
+                ctx = rank.self_attention(qkv, 1.0 / math.sqrt(D), key_mask)
+                present = (qkv[:, :, 1].permute(0, 2, 1, 3), qkv[:, :, 2].permute(0, 2, 1, 3))
+            return (ctx.reshape(N, La, self.all_head_size), present)
         if (not hooked and past_key_value is None
                 and ops.compute_dtype() == torch.bfloat16 and (hidden_states.is_cuda or hoisted_kv)):
             # fused projections: Q/K/V (self) or K/V (cross) as ONE GEMM over the shared input, and the attention
@@ -251,10 +272,10 @@ class BertAttention(nn.Module):
         self.pruned_heads = set()
 
     def forward(self, hidden_states, attention_mask=None, head_mask=None, encoder_hidden_states=None,
-                encoder_attention_mask=None, past_key_value=None, output_attentions=False):
+                encoder_attention_mask=None, past_key_value=None, output_attentions=False, rank=None):
         t = ops.GradTap()  # the residual gradient of hidden_states rides on the query / QKV projection's dX GEMM
         self_outputs = self.self(hidden_states, attention_mask, head_mask, encoder_hidden_states,
-                                 encoder_attention_mask, past_key_value, output_attentions, tap=t)
+                                 encoder_attention_mask, past_key_value, output_attentions, tap=t, rank=rank)
         attention_output = self.output(self_outputs[0], ops.tap(hidden_states, t))
         return (attention_output,) + self_outputs[1:]
 
@@ -328,8 +349,11 @@ class BertLayer(nn.Module):
                 layernorm_idx=0):
         decode = isinstance(past_key_value, ops.DecodeLayer)   # static decode cache: serves the cross-attention too
         self_past = past_key_value if decode else (past_key_value[:2] if past_key_value is not None else None)
+        rank = encoder_hidden_states if isinstance(encoder_hidden_states, ops.RankLayer) else None
+        if rank is not None and (past_key_value is not None or mode != "multimodal"):
+            raise RuntimeError("the ranking route serves the multimodal decoder without a cache")
         self_out = self.attention(hidden_states, attention_mask, head_mask, output_attentions=output_attentions,
-                                  past_key_value=self_past)
+                                  past_key_value=self_past, rank=rank)   # (the ranking route: its self-attention kernel too)
         attention_output = self_out[0]
         outputs = self_out[1:-1]
         present_key_value = self_out[-1]
@@ -357,6 +381,10 @@ _DECODE_CACHE = [os.environ.get("BQ_DECODE_CACHE", "1") != "0"]
 # reference's shape, profiles/generate_decode.md: the default since it won at both question lengths); BQ_DECODE_GRAPH=0: eager
 _DECODE_GRAPH = [os.environ.get("BQ_DECODE_GRAPH", "1") != "0"]
 _DECODE_STATS = {"sessions": 0, "captures": 0}   # decode sessions opened / steps captured so far (tests)
+# rank_answer on the K/V of the UNTILED question states + the candidate attention kernels (ops.RankShared, csrc/attn_rank.hip)
+# whenever the call is eligible (BertLMHeadModel.rank_shared).  BQ_RANK_SHARED=1 turns it on; off by default: faster at six of the
+# eight sizes of the A/B table, 1-4 % slower at two (profiles/rank_answer.md, tools/bench_rank.py)
+_RANK_SHARED = [os.environ.get("BQ_RANK_SHARED", "0") != "0"]
 _HOIST_CROSS_KV = True  # plain encoder / decoder: all layers' cross K/V in one GEMM
 
 
@@ -388,6 +416,10 @@ class BertEncoder(nn.Module):
             if mode != "multimodal" or forward_layers is not None or output_attentions or decode.hoisted is None:
                 raise RuntimeError("the decode cache serves the whole multimodal decoder without attention maps")
             hoisted = decode.hoisted
+        shared = encoder_hidden_states if isinstance(encoder_hidden_states, ops.RankShared) else None
+        if shared is not None and (mode != "multimodal" or forward_layers is not None or output_attentions
+                                   or past_key_values is not None or shared.hoisted.n != len(layers)):
+            raise RuntimeError("the ranking route serves the whole multimodal decoder without a cache or attention maps")
         key_only = lambda m: m is None or (m.dim() == 4 and m.shape[1] == 1 and m.shape[2] == 1)
         if (decode is None and _HOIST_CROSS_KV and mode == "multimodal" and len(layers) > 1 and past_key_values is None
                 and torch.is_tensor(encoder_hidden_states) and encoder_hidden_states.is_cuda
@@ -408,8 +440,11 @@ class BertEncoder(nn.Module):
             else:
                 past_key_value = past_key_values[i] if past_key_values is not None else None
             want = _wants(output_attentions, i, layers[-1])
-            layer_outputs = self.layer[i](hidden_states, attention_mask, None,
-                                          HoistedStates(hoisted, n) if hoisted is not None else encoder_hidden_states,
+            if shared is not None:
+                enc_i = shared.layer(n)
+            else:
+                enc_i = HoistedStates(hoisted, n) if hoisted is not None else encoder_hidden_states
+            layer_outputs = self.layer[i](hidden_states, attention_mask, None, enc_i,
                                           encoder_attention_mask, past_key_value, want, mode=mode,
                                           layernorm_idx=layernorm_idx)
             hidden_states = layer_outputs[0]
@@ -768,7 +803,11 @@ class BertModel(BertPreTrainedModel):
         attention_mask, ext_mask, past_len = self._prep(input_ids, inputs_embeds, encoder_embeds, attention_mask,
                                                         past_key_values, is_decoder, mask_prep)
         enc_ext = None
-        if encoder_hidden_states is not None:
+        if isinstance(encoder_hidden_states, ops.RankShared):
+            # (the ranking route: the question key mask is in the shared block, converted once; every sequence's own mask stays)
+            if encoder_attention_mask is not None or not is_decoder:
+                raise RuntimeError("the ranking route carries the question mask itself and serves a decoder")
+        elif encoder_hidden_states is not None:
             if encoder_attention_mask is None:
                 enc_ext = self._prepared(mask_prep, "enc_ext", (encoder_hidden_states.shape[0], 1, 1, encoder_hidden_states.shape[1]))
                 if enc_ext is None:
@@ -989,6 +1028,40 @@ class BertLMHeadModel(BertPreTrainedModel):
             mask = _ext.key_mask_log2(self.invert_attention_mask(em), S, enc.shape[1])
         cache = ops.DecodeCache(len(layers), S, max_length, H, enc.device, hoisted, mask)
         return DecodeSession(self, cache, _DECODE_GRAPH[0] if graph is None else graph)
+
+    def rank_shared(self, question_states, question_atts, answer_ids, answer_atts, k):
+        """An ops.RankShared for ranking the candidates answer_ids (n_ans, La) against question_states (Bq, Lq, hidden) -- the
+        first-token pass with group = 1, the re-score of k candidates per question with group = k --, or None when the call is
+        not eligible: everything is checked HERE, before the first layer runs.  Eligible: the switch on, eval mode (the kernels
+        have no dropout), grad mode off and states that do not require grad (there is no backward), candidates given as
+        (n_ans, La) ids with an (n_ans, La) key mask (the causal mask is then factored), bf16 compute dtype, CUDA tensors, head size 64, La <=
+        RANK_LMAX, question states given as a tensor with a (Bq, Lq) key mask (or none), k >= 1 (the re-score then has
+        N = Bq * k sequences by construction), no save_attention hook, no output_attentions, fp32 nn.Parameter weights with
+        biases in every attention projection.  The hoisted cross K/V projections of all layers (Bq * Lq rows, not
+        Bq * k * Lq) and the mask conversion run now, once."""
+        from . import _ext
+        qs, qm = question_states, question_atts
+        layers = list(self.bert.encoder.layer)
+        cfg = self.config
+        if not (_RANK_SHARED[0] and not self.training and not torch.is_grad_enabled() and torch.is_tensor(qs)
+                and not qs.requires_grad and torch.is_tensor(answer_atts) and answer_atts.is_cuda
+                and torch.is_tensor(answer_ids) and tuple(answer_atts.shape) == tuple(answer_ids.shape)
+                and ops.compute_dtype() == torch.bfloat16 and qs.is_cuda and qs.dim() == 3 and qs.shape[0] > 0 and qs.shape[1] > 0
+                and (qm is None or (torch.is_tensor(qm) and qm.is_cuda and tuple(qm.shape) == tuple(qs.shape[:2])))
+                and torch.is_tensor(answer_ids) and answer_ids.is_cuda and answer_ids.dim() == 2
+                and 1 <= answer_ids.shape[1] <= _ext.RANK_LMAX and int(k) >= 1
+                and cfg.hidden_size // cfg.num_attention_heads == 64 and not cfg.output_attentions
+                and all(hasattr(l, "crossattention") for l in layers)):
+            return None
+        for l in layers:
+            sa, ca = l.attention.self, l.crossattention.self
+            if sa.save_attention or ca.save_attention:
+                return None
+            for lin in (sa.query, sa.key, sa.value, ca.query, ca.key, ca.value):
+                if lin.bias is None or not ops._param_ok(lin.weight, lin.bias):
+                    return None
+        mask = None if qm is None else self.invert_attention_mask(qm)
+        return ops.RankShared(qs, [l.crossattention.self for l in layers], cfg.num_attention_heads, mask)
 
     @torch.no_grad()
     def generate(self, input_ids, max_length=20, min_length=0, num_beams=1, eos_token_id=None, pad_token_id=None,

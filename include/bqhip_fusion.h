@@ -110,6 +110,26 @@ BQ_API int bq_attn_decode_cross(const void *Q, const void *K, const void *V, voi
                                 int Lkp, long q_bs, long q_hs, long k_bs, long k_rs, long k_hs, long o_bs, long o_hs,
                                 float scale, void *stream);
 
+/* ---- attention of answer ranking: N = Bq * group short candidate sequences that share the K / V of their question
+ * (csrc/attn_rank.hip; additive to ABI 6) ----
+ * Replaces, in the re-score of models/blip_vqa_3d.py:509-566 (rank_answer), the attention of models/med.py:179-217 over
+ * question states tiled k times: one wave per (sequence, head), head dim 64, bf16 operands, fp32 scores and softmax
+ * (scale * log2 e folded in, exp2), bf16 output; no LDS, no atomics, fixed reduction trees (bitwise reproducible).
+ * bq_attn_rank_self: causal self-attention on the packed projection qkv (N, La, 3, H, 64) by strides q_bs / q_rs / q_ks / q_hs
+ *   (sequence, token, q-k-v axis, head), La <= BQ_RANK_LMAX (more: BQ_ELIMIT).  Query i sees key j iff j <= i; mask NULL or f32
+ *   (N, Lap) additive key mask times log2(e), Lap >= La, finite values.  O (N, La, H, 64) by strides o_bs / o_rs / o_hs.
+ * bq_attn_rank_cross: Q (N, La, H, 64), K / V (Bq, Lk, H, 64) by strides as in bq_attn_fwd (a hoisted (Bq, Lk, 2, H, 64) block);
+ *   sequence n reads question n / group, N == Bq * group (else BQ_EINVAL); mask NULL or f32 (Bq, Lkp), Lkp >= Lk; any
+ *   Lk >= 1 (chunks of 32, online softmax); a wave carries BQ_RANK_QBLOCK queries through each loaded chunk.
+ * All strides in elements and multiples of 8, pointers 16-byte aligned.  N == 0: no-op. */
+#define BQ_RANK_LMAX 32
+#define BQ_RANK_QBLOCK 4
+BQ_API int bq_attn_rank_self(const void *qkv, void *O, const float *mask, int N, int H, int La, int Lap, long q_bs, long q_rs,
+                             long q_ks, long q_hs, long o_bs, long o_rs, long o_hs, float scale, void *stream);
+BQ_API int bq_attn_rank_cross(const void *Q, const void *K, const void *V, void *O, const float *mask, int N, int Bq, int group,
+                              int H, int La, int Lk, int Lkp, long q_bs, long q_rs, long q_hs, long k_bs, long k_rs, long k_hs,
+                              long o_bs, long o_rs, long o_hs, float scale, void *stream);
+
 /* ---- y = LayerNorm(path(dropout(x)) + residual) (csrc/ln.hip) -----------------------------------------------
  * Replaces  hidden = dense(x); hidden = dropout(hidden); hidden = LayerNorm(hidden + input)
  *   models/med.py:236-239 (BertSelfOutput), :313-317 (BertOutput)   [residual != NULL, p_drop]
