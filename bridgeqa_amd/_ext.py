@@ -1049,6 +1049,68 @@ def nms(box, score, thresh, cls=None, valid=None, old_type=False, same_cls=False
     return keep.bool()
 
 
+# ---- detection mAP (csrc/ap_eval.hip) --------------------------------------------------------------------
+_d = ctypes.c_double
+_lib.bq_ap_match.argtypes = [_vp] * 5 + [ctypes.POINTER(_d)] + [_vp] * 3 + [_i] * 6 + [_vp]
+_lib.bq_ap_match.restype = ctypes.c_int
+_lib.bq_ap_curve.argtypes = [_vp] * 7 + [_i] * 3 + [_vp]
+_lib.bq_ap_curve.restype = ctypes.c_int
+
+
+def _ap_req(t, dtype, shape_tail, name):
+    if not t.is_cuda:
+        raise RuntimeError("%s: CPU not supported" % name)
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape[1:]) != shape_tail:
+        raise RuntimeError("%s must be a contiguous %s tensor of shape (n%s)" % (name, dtype, "".join(", %d" % s for s in shape_tail)))
+
+
+def ap_match(box_tab, det_box, gt_tab, seg_det, seg_gt, thresholds, max_seg_gt=None):
+    """box_tab f64 (Nb, 6), det_box i32 (D), gt_tab f64 (G, 6), seg_det / seg_gt i32 (S + 1) CSR offsets, thresholds: up to
+    4 floats -> tp u8 (T, D), ovmax f64 (D), jmax i32 (D).  max_seg_gt: the largest segment's ground-truth count when the
+    caller knows a bound (no synchronisation); None reads it from seg_gt (one device -> host copy)."""
+    _ap_req(box_tab, torch.float64, (6,), "box_tab")
+    _ap_req(det_box, torch.int32, (), "det_box")
+    _ap_req(gt_tab, torch.float64, (6,), "gt_tab")
+    _ap_req(seg_det, torch.int32, (), "seg_det")
+    _ap_req(seg_gt, torch.int32, (), "seg_gt")
+    if seg_det.numel() != seg_gt.numel() or seg_det.numel() < 1:
+        raise RuntimeError("ap_match: seg_det %d and seg_gt %d offsets" % (seg_det.numel(), seg_gt.numel()))
+    thr = [float(t) for t in thresholds]
+    T, D, S = len(thr), det_box.numel(), seg_det.numel() - 1
+    if max_seg_gt is None:
+        max_seg_gt = int((seg_gt[1:] - seg_gt[:-1]).max().item()) if S > 0 else 0
+    with torch.cuda.device(box_tab.device):
+        dev = box_tab.device
+        tp = torch.zeros(max(T, 1), D, dtype=torch.uint8, device=dev)
+        ovmax = torch.full((D,), float("-inf"), dtype=torch.float64, device=dev)
+        jmax = torch.full((D,), -1, dtype=torch.int32, device=dev)
+        _check(_lib.bq_ap_match(_p(box_tab), _p(det_box), _p(gt_tab), _p(seg_det), _p(seg_gt), (_d * max(T, 1))(*thr),
+                                _p(tp), _p(ovmax), _p(jmax), box_tab.shape[0], D, gt_tab.shape[0], S, T, int(max_seg_gt),
+                                _stream()), "ap_match")
+    return tp, ovmax, jmax
+
+
+def ap_curve(tp, cls_off, npos):
+    """tp u8 (T, D) in curve order, cls_off i32 (C + 1), npos f64 (C) -> rec, prec f64 (T, D), ap, last_recall f64 (C, T)"""
+    if tp.dim() != 2:
+        raise RuntimeError("tp must be (T, D)")
+    _ap_req(tp, torch.uint8, (tp.shape[1],), "tp")
+    _ap_req(cls_off, torch.int32, (), "cls_off")
+    _ap_req(npos, torch.float64, (), "npos")
+    T, D = tp.shape
+    C = npos.numel()
+    if cls_off.numel() != C + 1:
+        raise RuntimeError("ap_curve: %d class offsets for %d classes" % (cls_off.numel(), C))
+    with torch.cuda.device(tp.device):
+        rec = torch.zeros(T, D, dtype=torch.float64, device=tp.device)
+        prec = torch.zeros(T, D, dtype=torch.float64, device=tp.device)
+        ap = torch.zeros(C, T, dtype=torch.float64, device=tp.device)
+        last = torch.zeros(C, T, dtype=torch.float64, device=tp.device)
+        _check(_lib.bq_ap_curve(_p(tp), _p(cls_off), _p(npos), _p(rec), _p(prec), _p(ap), _p(last), D, C, T, _stream()),
+               "ap_curve")
+    return rec, prec, ap, last
+
+
 # ---- multiview projection (csrc/projection.hip) ---------------------------------------------------------
 _lib.bq_project_points.argtypes = [_vp] * 4 + [_i] * 4 + [_f] * 7 + [_vp]
 _lib.bq_project_points.restype = ctypes.c_int

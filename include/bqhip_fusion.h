@@ -314,6 +314,30 @@ BQ_API int bq_box_point_count(const float *points, const float *center, const fl
 BQ_API int bq_nms(const float *box, const float *score, const int *cls, const unsigned char *valid, unsigned char *keep,
                   int B, int K, float thresh, int old_type, int same_cls, void *stream);
 
+/* ---- detection mAP (csrc/ap_eval.hip) ----------------------------------------------------------------------------
+ * Replaces the host loops of utils/eval_det.py:57-141 eval_det_cls / :4-35 voc_ap (non-07 metric) over
+ * utils/box_util.py:112-123 box3d_iou, as lib/ap_helper.py:225-278 APCalculator drives them.  Double arithmetic, every
+ * operation rounded separately: overlaps, recall and precision equal numpy's bit for bit.
+ * bq_ap_match: greedy matching, one wave per segment = one (class, scene) pair.  box_tab f64 (Nb, 6) axis-aligned extents
+ *   (xmin, ymin, zmin, xmax, ymax, zmax); det_box i32 (D) rows of box_tab, the detections of a segment contiguous and
+ *   ordered by (score descending, list position ascending); gt_tab f64 (G, 6), a segment's boxes contiguous; seg_det /
+ *   seg_gt i32 (S + 1) CSR offsets; thresholds: T <= 4 doubles in HOST memory (read before the launch).  Out: tp u8
+ *   (T, D) -- 1 iff the best overlap exceeds the threshold and its box is not yet taken for that threshold; ovmax f64 (D)
+ *   the best overlap (-inf without ground truth); jmax i32 (D) its segment-local index, lowest on equal overlaps (-1
+ *   without ground truth).  max_seg_gt: the caller's bound on a segment's ground-truth boxes, <= 2048 (BQ_ELIMIT beyond;
+ *   a segment that exceeds the bound after all is not matched: tp 0, ovmax NaN, jmax -2).  Detections outside every
+ *   segment are not written.
+ * bq_ap_curve: one workgroup per (class, threshold).  tp u8 (T, D) in curve order (class, score descending, scene
+ *   ascending, list position ascending); cls_off i32 (C + 1); npos f64 (C) ground-truth boxes per class.  Out: rec / prec
+ *   f64 (T, D) = cumulative tp / (npos + 1e-8) and tp / max(tp + fp, DBL_EPSILON); ap / last_recall f64 (C, T): the area
+ *   under the precision envelope, summed in a fixed order (the same bits on every run), and the last recall value; both 0
+ *   for a class without detections. */
+BQ_API int bq_ap_match(const double *box_tab, const int *det_box, const double *gt_tab, const int *seg_det,
+                       const int *seg_gt, const double *thresholds, unsigned char *tp, double *ovmax, int *jmax, int Nb,
+                       int D, int G, int S, int T, int max_seg_gt, void *stream);
+BQ_API int bq_ap_curve(const unsigned char *tp, const int *cls_off, const double *npos, double *rec, double *prec,
+                       double *ap, double *last_recall, int D, int C, int T, void *stream);
+
 /* ---- multiview projection (csrc/projection.hip) ---------------------------------------------------------------------
  * Replaces the per-frame host loop of lib/projection.py:194-252 ProjectionHelper.compute_projection / :254-276 project
  * as driven by scripts/project_multiview_features.py:103-202 (offline preprocessing).
