@@ -12,6 +12,8 @@ import os
 
 import torch  # must be imported first: libbqhip.so resolves libamdhip64.so.7 to torch's copy
 
+from . import _cabi
+
 # (BQHIP_LIB: another build of the same sources, e.g. with a measurement macro set -- A/B runs in one gpurun call)
 _LIB_PATH = os.environ.get("BQHIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libbqhip.so")
 
@@ -21,64 +23,14 @@ if not os.path.exists(_LIB_PATH):
         "(hipcc --offload-arch=gfx950). There is no CPU fallback." % _LIB_PATH)
 
 _lib = ctypes.CDLL(_LIB_PATH)
-_lib.bq_last_error.restype = ctypes.c_char_p
-_lib.bq_abi_version.restype = ctypes.c_int
-ABI_VERSION = 6   # = BQHIP_ABI_VERSION of include/bqhip.h
+# Every prototype, descriptor struct and integer constant below comes from include/bqhip.h and include/bqhip_fusion.h (_cabi.py).
+_D = _cabi.DEFINES
+_cabi.bind(_lib, ("bq_abi_version", "bq_last_error"))
+ABI_VERSION = _D["BQHIP_ABI_VERSION"]
 if _lib.bq_abi_version() != ABI_VERSION:
     raise ImportError("bridgeqa_amd: libbqhip.so ABI %d != %d (stale library: python -m bridgeqa_amd.build --force)"
                       % (_lib.bq_abi_version(), ABI_VERSION))
-
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_SIGS = {
-    "bq_opt_n_threads": [_i],
-    "bq_furthest_point_sampling": [_vp, _vp, ctypes.c_size_t, _vp, _i, _i, _i, _vp],
-    "bq_furthest_point_sampling_bruteforce": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "bq_gather_points": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "bq_gather_points_grad": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "bq_ball_query": [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "bq_ball_query_background": [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "bq_group_points": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "bq_group_points_grad": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "bq_three_nn": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "bq_three_nn_dist": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "bq_three_interpolate": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "bq_three_interpolate_grad": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "bq_group_concat": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
-    "bq_group_concat_grad": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
-    "bq_group_concat_bf16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
-    "bq_group_concat_grad_bf16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
-}
-for _name, _args in _SIGS.items():
-    getattr(_lib, _name).argtypes = _args
-    getattr(_lib, _name).restype = ctypes.c_int
-_l = ctypes.c_long
-_u = ctypes.c_uint
-_lib.bq_attn_fwd.argtypes = [_vp] * 6 + [_i] * 5 + [_l] * 9 + [_f, _f, _u, _vp, _i, _vp]
-_lib.bq_attn_fwd.restype = ctypes.c_int
-_lib.bq_attn_bwd.argtypes = [_vp] * 11 + [_i] * 5 + [_l] * 9 + [_f, _f, _u, _vp, _i, _vp]
-_lib.bq_attn_bwd.restype = ctypes.c_int
-_lib.bq_attn_set_persistent.argtypes = [_i]
-_lib.bq_attn_set_persistent.restype = ctypes.c_int
-_lib.bq_attn_probs.argtypes = [_vp] * 5 + [_i] * 5 + [_l] * 6 + [_f, _f, _u, _vp, _i, _vp]
-_lib.bq_attn_probs.restype = ctypes.c_int
-_lib.bq_drop_add_ln_fwd.argtypes = [_vp] * 9 + [_i, _i, _f, _f, _f, _i, _u, _vp, _vp]
-_lib.bq_drop_add_ln_fwd.restype = ctypes.c_int
-_lib.bq_drop_add_ln_bwd.argtypes = [_vp] * 10 + [_i, _i, _f, _f, _f, _i, _u, _vp, _vp]
-_lib.bq_drop_add_ln_bwd.restype = ctypes.c_int
-_lib.bq_drop_add_ln_bwd_sum.argtypes = [_vp] * 9 + [_i, _i, _f, _f, _i, _u, _vp, _vp]
-_lib.bq_drop_add_ln_bwd_sum.restype = ctypes.c_int
-_lib.bq_twin_drop_add_ln_fwd.argtypes = [_vp] * 10 + [_i, _i, _f, _f, _u, _vp, _vp]
-_lib.bq_twin_drop_add_ln_fwd.restype = ctypes.c_int
-_lib.bq_twin_drop_add_ln_bwd.argtypes = [_vp] * 10 + [_i, _i, _f, _f, _u, _vp, _vp]
-_lib.bq_twin_drop_add_ln_bwd.restype = ctypes.c_int
-_lib.bq_fps_workspace_bytes.argtypes = [_i, _i]
-_lib.bq_fps_workspace_bytes.restype = ctypes.c_size_t
-_lib.bq_drop_add_ln_bwd_det_slab_floats.argtypes = [_i, _i, _i]
-_lib.bq_drop_add_ln_bwd_det_slab_floats.restype = _l
-_lib.bq_drop_add_ln_bwd_det.argtypes = [_vp] * 4 + [_i] + [_vp] * 8 + [_i, _i, _f, _f, _f, _i, _u, _vp, _i, _vp]
-_lib.bq_drop_add_ln_bwd_det.restype = ctypes.c_int
-_lib.bq_gemm_splitk_fold_det.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp]
-_lib.bq_gemm_splitk_fold_det.restype = ctypes.c_int
+_cabi.bind(_lib)
 
 # ---- the deterministic training mode (bridgeqa_amd.set_deterministic) ------------------------------------------------------------
 # Every site of the training path where float atomics from several workgroups met on one address, the entry point that takes it in
@@ -218,12 +170,6 @@ def ball_query(new_xyz, xyz, radius, nsample, background=False):
 
 
 BALL_QUERY_GRID_MIN_N = [8192]   # scenes from this size on go through the grid (tests / tools set it to compare the two paths)
-_lib.bq_ball_query_grid_workspace_bytes.argtypes = [_i, _i]
-_lib.bq_ball_query_grid_workspace_bytes.restype = ctypes.c_size_t
-_lib.bq_ball_query_grid.argtypes = [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, ctypes.c_size_t, _vp]
-_lib.bq_ball_query_grid.restype = ctypes.c_int
-_lib.bq_ball_query_grid_build_mode.argtypes = [_i]
-_lib.bq_ball_query_grid_build_mode.restype = ctypes.c_int
 
 
 def ball_query_grid_build_mode(multi):
@@ -327,12 +273,6 @@ def group_concat_grad(grad_out, idx, n, radius, normalize, need_features, need_x
         _check(fn(_p(grad_out), _p(idx), _p(gf), _p(gx), _p(gn), B, C, int(n), M, S,
                   float(radius), int(bool(normalize)), _stream()), "group_concat_grad")
     return gf, gx, gn
-
-
-_lib.bq_group_concat_pm.argtypes = [_vp, _vp, _vp, ctypes.c_long, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]
-_lib.bq_group_concat_pm.restype = ctypes.c_int
-_lib.bq_group_concat_pm_grad.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]
-_lib.bq_group_concat_pm_grad.restype = ctypes.c_int
 
 
 def group_concat_pm(xyz, new_xyz, feats_pm, idx, radius, normalize, out_dtype, pad_to=1):
@@ -469,10 +409,6 @@ def attn_bwd(q, k, v, out, lse, grad_out, scale, dq, dk, dv, mask_log2=None, p_d
 
 
 # ---- single-query decode attention over a static cache (csrc/attn_decode.hip) ------------------------------------------------
-_lib.bq_attn_decode_self.argtypes = [_vp] * 5 + [_i] * 4 + [_l] * 9 + [_f, _vp]
-_lib.bq_attn_decode_self.restype = ctypes.c_int
-_lib.bq_attn_decode_cross.argtypes = [_vp] * 5 + [_i] * 4 + [_l] * 7 + [_f, _vp]
-_lib.bq_attn_decode_cross.restype = ctypes.c_int
 DECODE_CHUNK = 32        # keys per online-softmax step of attn_decode_kernel (DEC_CHUNK)
 DECODE_CALLS = [0, 0]    # launches of attn_decode_self / attn_decode_cross so far (tests assert the route taken)
 
@@ -552,12 +488,8 @@ def attn_decode_cross(q, kv, scale, mask_log2=None, out=None):
 
 
 # ---- attention of answer ranking: candidate sequences sharing their question's K / V (csrc/attn_rank.hip) -------------------------
-_lib.bq_attn_rank_self.argtypes = [_vp] * 3 + [_i] * 4 + [_l] * 7 + [_f, _vp]
-_lib.bq_attn_rank_self.restype = ctypes.c_int
-_lib.bq_attn_rank_cross.argtypes = [_vp] * 5 + [_i] * 7 + [_l] * 9 + [_f, _vp]
-_lib.bq_attn_rank_cross.restype = ctypes.c_int
-RANK_LMAX = 32         # tokens per sequence attn_rank_self holds in registers (BQ_RANK_LMAX)
-RANK_QBLOCK = 4        # queries a wave of attn_rank_cross carries through one loaded K / V chunk (BQ_RANK_QBLOCK)
+RANK_LMAX = _D["BQ_RANK_LMAX"]       # tokens per sequence attn_rank_self holds in registers
+RANK_QBLOCK = _D["BQ_RANK_QBLOCK"]   # queries a wave of attn_rank_cross carries through one loaded K / V chunk
 RANK_CALLS = [0, 0]    # launches of attn_rank_self / attn_rank_cross that the library accepted (tests assert the route taken)
 # (contract of both wrappers, relied on by tests/test_attn_rank_cpu.py: between the is_cuda checks and the last operand check
 # nothing touches the device -- only shape, dtype, stride and data_ptr are read)
@@ -632,17 +564,7 @@ def attn_rank_cross(q, kv, scale, group, mask_log2=None, out=None):
     return out
 
 
-class _AttnSide(ctypes.Structure):
-    _fields_ = [("Q", _vp), ("K", _vp), ("V", _vp), ("dO", _vp), ("O", _vp), ("out", _vp), ("dK", _vp), ("dV", _vp),
-                ("LSE", _vp), ("DELTA", _vp), ("mask", _vp), ("Lq", _i), ("Lk", _i), ("Lkp", _i),
-                ("q_bs", _l), ("q_rs", _l), ("q_hs", _l), ("k_bs", _l), ("k_rs", _l), ("k_hs", _l),
-                ("o_bs", _l), ("o_rs", _l), ("o_hs", _l), ("seed", _u)]
-
-
-_lib.bq_attn_fwd_pair.argtypes = [ctypes.POINTER(_AttnSide), _i, _i, _f, _f, _vp, _vp]
-_lib.bq_attn_fwd_pair.restype = ctypes.c_int
-_lib.bq_attn_bwd_pair.argtypes = [ctypes.POINTER(_AttnSide), _i, _i, _f, _f, _vp, _vp]
-_lib.bq_attn_bwd_pair.restype = ctypes.c_int
+_AttnSide = _cabi.STRUCTS["bq_attn_side"]
 
 
 def attn_pair_ok(qa, ka, qb, kb):
@@ -705,12 +627,6 @@ def attn_bwd_pair(sides, scale, p_drop=0.0, seed_tensor=None):
         _check(_lib.bq_attn_bwd_pair(arr, B, H, float(scale), float(p_drop), _p(seed_tensor), _stream()), "attn_bwd_pair")
 
 
-_lib.bq_attn_fwd2.argtypes = [_vp] * 8 + [_i] * 6 + [_l] * 12 + [_f, _f, _u, _vp, _vp]
-_lib.bq_attn_fwd2.restype = ctypes.c_int
-_lib.bq_attn_bwd2.argtypes = [_vp] * 15 + [_i] * 6 + [_l] * 12 + [_f, _f, _u, _vp, _vp]
-_lib.bq_attn_bwd2.restype = ctypes.c_int
-
-
 def key_mask_log2_two(mask, B, Lk1, Lk2):
     """additive key mask broadcastable to (B,1,1,Lk1+Lk2) over cat(segment 1, segment 2) -> f32 (B, pad64(Lk1) +
     pad64(Lk2)) in the two-segment layout of bq_attn_fwd2 (each segment padded to a multiple of 64), times log2(e)"""
@@ -771,11 +687,6 @@ def attn_bwd2(q, k1, v1, k2, v2, out, lse, grad_out, scale, dq, dk1, dv1, dk2, d
                "attn_bwd2")
 
 
-_lib.bq_colsum_chunks.argtypes = [_i]
-_lib.bq_colsum_chunks.restype = ctypes.c_int
-_lib.bq_colsum_bf16.argtypes = [_vp, _vp, _i, _i, _vp, _vp, _vp]
-_lib.bq_colsum_bf16.restype = ctypes.c_int
-
 _COLSUM_SLOTS = 1 << 16
 _colsum_counters = {}
 _colsum_next = [0]
@@ -808,10 +719,6 @@ def colsum(g2d):
     return out
 
 
-_lib.bq_gelu_fwd_bf16.argtypes = [_vp, _vp, _l, _vp]
-_lib.bq_gelu_fwd_bf16.restype = ctypes.c_int
-
-
 def gelu_fwd(x):
     """exact GELU of a contiguous bf16 tensor (numel % 8 == 0)"""
     with torch.cuda.device(x.device):
@@ -821,10 +728,6 @@ def gelu_fwd(x):
 
 
 # ---- multi-tensor AdamW that also writes the bf16 shadows (csrc/adamw.hip) -----------------------------
-_lib.bq_adamw_chunk_elems.restype = ctypes.c_int
-_lib.bq_adamw_tensor_bytes.restype = ctypes.c_int
-_lib.bq_adamw_multi.argtypes = [_vp, _vp, _i, _vp, _f, _f, _f, _f, _vp]
-_lib.bq_adamw_multi.restype = ctypes.c_int
 ADAMW_CHUNK = _lib.bq_adamw_chunk_elems()
 ADAMW_TENSOR_BYTES = _lib.bq_adamw_tensor_bytes()
 
@@ -838,9 +741,6 @@ def adamw_multi(table, chunks, step, beta1, beta2, eps, grad_clip_value=0.0):
 
 
 # ---- multi-tensor bf16 transpose (csrc/transpose.hip): the K-contiguous copies of the text side's weights -------
-_lib.bq_transpose_tensor_bytes.restype = ctypes.c_int
-_lib.bq_transpose_multi_bf16.argtypes = [_vp, _vp, _i, _i, _vp]
-_lib.bq_transpose_multi_bf16.restype = ctypes.c_int
 TRANSPOSE_TENSOR_BYTES = _lib.bq_transpose_tensor_bytes()
 
 
@@ -870,14 +770,6 @@ def transpose_multi(table, chunks, max_wgs=0):
 
 
 # ---- training-mode BatchNorm + ReLU (+ max over nsample) on point-major bf16 rows (csrc/bn.hip) -------
-_lib.bq_bn_chunks.argtypes = [_l, _i, _i]
-_lib.bq_bn_chunks.restype = ctypes.c_int
-_lib.bq_bn_stats.argtypes = [_vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]
-_lib.bq_bn_stats.restype = ctypes.c_int
-_lib.bq_bn_apply.argtypes = [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp]
-_lib.bq_bn_apply.restype = ctypes.c_int
-_lib.bq_bn_backward.argtypes = [_vp] * 9 + [_l, _i, _i, _i, _i, _vp]
-_lib.bq_bn_backward.restype = ctypes.c_int
 
 
 def bn_relu_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, S, relu, pool):
@@ -1011,10 +903,6 @@ def twin_drop_add_ln_bwd(x, residual, gamma, gamma2, dy, mean, rstd, eps, p_drop
 
 
 # ---- proposal post-processing (csrc/nms.hip) ------------------------------------------------------------
-_lib.bq_box_point_count.argtypes = [_vp] * 5 + [_i] * 5 + [_vp]
-_lib.bq_box_point_count.restype = ctypes.c_int
-_lib.bq_nms.argtypes = [_vp] * 5 + [_i, _i, _f, _i, _i, _vp]
-_lib.bq_nms.restype = ctypes.c_int
 
 
 def box_point_count(points, center, size, heading, cap=0):
@@ -1051,10 +939,6 @@ def nms(box, score, thresh, cls=None, valid=None, old_type=False, same_cls=False
 
 # ---- detection mAP (csrc/ap_eval.hip) --------------------------------------------------------------------
 _d = ctypes.c_double
-_lib.bq_ap_match.argtypes = [_vp] * 5 + [ctypes.POINTER(_d)] + [_vp] * 3 + [_i] * 6 + [_vp]
-_lib.bq_ap_match.restype = ctypes.c_int
-_lib.bq_ap_curve.argtypes = [_vp] * 7 + [_i] * 3 + [_vp]
-_lib.bq_ap_curve.restype = ctypes.c_int
 
 
 def _ap_req(t, dtype, shape_tail, name):
@@ -1112,10 +996,6 @@ def ap_curve(tp, cls_off, npos):
 
 
 # ---- multiview projection (csrc/projection.hip) ---------------------------------------------------------
-_lib.bq_project_points.argtypes = [_vp] * 4 + [_i] * 4 + [_f] * 7 + [_vp]
-_lib.bq_project_points.restype = ctypes.c_int
-_lib.bq_fuse_point_features.argtypes = [_vp] * 3 + [_i] * 5 + [_vp]
-_lib.bq_fuse_point_features.restype = ctypes.c_int
 
 
 def project_points(points, depth, frames, image_dims, fx, fy, cx, cy, depth_min, depth_max, accuracy):
@@ -1155,20 +1035,11 @@ def fuse_point_features(pix, feat, maxpool):
 
 
 # ---- MFMA bf16 GEMM family (csrc/gemm.hip) ------------------------------------------------------------
-GEMM_P_XC, GEMM_Q_XC, GEMM_OUT_F32, GEMM_BACKGROUND = 1, 2, 4, 8
-EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_CE, EPI_ADD = 0, 1, 2, 3, 4, 5
-GEMM_DET = 16   # BQ_GEMM_DET: set by gemm_grouped itself in the deterministic mode
-
-
-class _GemmDesc(ctypes.Structure):
-    _fields_ = [("P", _vp), ("Q", _vp), ("out", _vp), ("bias", _vp), ("out2", _vp), ("aux", _vp), ("colsum", _vp),
-                ("ldp", _i), ("ldq", _i), ("ldo", _i), ("Ni", _i), ("Nj", _i), ("Kc", _i), ("bias_bf16", _i), ("p_bytes", _l), ("q_bytes", _l), ("ksplit", _i),
-                ("q_rpb", _i), ("q_bstride", _i), ("o_rpb", _i), ("o_bstride", _i), ("accum", _i)]
-
-
-_lib.bq_gemm_bf16.argtypes = [ctypes.POINTER(_GemmDesc), _i, _i, _i, _i, _vp]
-_lib.bq_gemm_bf16.restype = ctypes.c_int
-_lib.bq_gemm_max_problems.restype = ctypes.c_int
+GEMM_P_XC, GEMM_Q_XC, GEMM_OUT_F32, GEMM_BACKGROUND = (_D["BQ_GEMM_" + n] for n in ("P_XC", "Q_XC", "OUT_F32", "BACKGROUND"))
+EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_CE, EPI_ADD = (
+    _D["BQ_GEMM_EPI_" + n] for n in ("NONE", "BIAS", "BIAS_GELU", "DGELU", "BIAS_CE", "ADD"))
+GEMM_DET = _D["BQ_GEMM_DET"]   # set by gemm_grouped itself in the deterministic mode
+_GemmDesc = _cabi.STRUCTS["bq_gemm_desc"]
 GEMM_TILE_ROWS = 1024  # problems with at least this many j rows (and i columns >= 256) run on the large-tile kernels
 # Large problems whose output is bf16 with a K-contiguous Q (forward, input gradient) take the 256 x 128 persistent kernel
 # (csrc/gemm_mid.hip: two workgroups per CU; round 3 A/B against the 256 x 256 one: 38.8 vs 39.2 ms per c3 step).
@@ -1338,11 +1209,6 @@ STREAMK = [False]   # the 256 x 128 kernel's stream-K form: built, parity-green,
 # BQ_GEMM_STREAMK256=1 switches it on
 STREAMK256 = [os.environ.get("BQ_GEMM_STREAMK256", "0") == "1"]
 _SK_WS = {}
-_lib.bq_gemm_workspace_bytes.restype = ctypes.c_long
-_lib.bq_gemm_set_workspace.argtypes = [_vp, ctypes.c_long, _vp]
-_lib.bq_gemm_set_workspace.restype = ctypes.c_int
-_lib.bq_gemm_streamk_mode.argtypes = [_i]
-_lib.bq_gemm_streamk_mode.restype = ctypes.c_int
 
 
 def _streamk_apply():
@@ -1421,18 +1287,7 @@ def gemm_dw(dy, x, tile=None):
     return dw
 
 
-class _ColsumDesc(ctypes.Structure):
-    _fields_ = [("g", _vp), ("out", _vp), ("M", _i), ("N", _i), ("ld", _i)]
-
-
-_lib.bq_colsum_grouped_bf16.argtypes = [ctypes.POINTER(_ColsumDesc), _i, _vp]
-_lib.bq_colsum_grouped_bf16.restype = ctypes.c_int
-
-
-_lib.bq_colsum_grouped_det_floats.argtypes = [ctypes.POINTER(_ColsumDesc), _i]
-_lib.bq_colsum_grouped_det_floats.restype = _l
-_lib.bq_colsum_grouped_det_bf16.argtypes = [ctypes.POINTER(_ColsumDesc), _i, _vp, _vp]
-_lib.bq_colsum_grouped_det_bf16.restype = ctypes.c_int
+_ColsumDesc = _cabi.STRUCTS["bq_colsum_desc"]
 
 
 def _colsum_grouped_into(mats, outs, site):
@@ -1482,14 +1337,6 @@ def colsum_grouped(mats):
     return outs
 
 
-_lib.bq_wgrad_rows_supported.argtypes = [_i, _i]
-_lib.bq_wgrad_rows_supported.restype = ctypes.c_int
-_lib.bq_wgrad_rows_workgroups.argtypes = [_l, _i, _i, _i]
-_lib.bq_wgrad_rows_workgroups.restype = ctypes.c_int
-_lib.bq_wgrad_rows_bf16.argtypes = [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]
-_lib.bq_wgrad_rows_bf16.restype = ctypes.c_int
-
-
 def wgrad_rows_ok(Ni, Nj):
     return bool(_lib.bq_wgrad_rows_supported(int(Ni), int(Nj)))
 
@@ -1510,11 +1357,6 @@ def wgrad_rows(x, dy, out, workgroups=0):
 
 
 # ---- SharedMLP layer on point-major rows: 1x1 convolution + BatchNorm statistics in its epilogue (csrc/gemm.hip) ----
-_lib.bq_pwconv_records.argtypes = [_l, _i]
-_lib.bq_pwconv_records.restype = ctypes.c_int
-_lib.bq_pwconv_bn_fwd.argtypes = [_vp, _l, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp,
-                                  _vp, _vp, _vp]
-_lib.bq_pwconv_bn_fwd.restype = ctypes.c_int
 
 
 def pwconv_bn_relu_fwd(x, K, w_pad, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, S, relu,
@@ -1562,32 +1404,11 @@ def pwconv_bn_relu_fwd(x, K, w_pad, gamma, beta, running_mean, running_var, num_
 
 
 # ---- the backward of a SharedMLP layer in one pass over its activations (csrc/detbwd.hip) ------------------------------------
-_lib.bq_bn_apply_arg.argtypes = [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp]
-_lib.bq_bn_apply_arg.restype = ctypes.c_int
-_lib.bq_bn_backward_reduce.argtypes = [_vp] * 8 + [_l, _i, _i, _i, _i, _vp]
-_lib.bq_bn_backward_reduce.restype = ctypes.c_int
-_lib.bq_bn_backward_reduce_arg.argtypes = [_vp] * 9 + [_l, _i, _i, _i, _vp]
-_lib.bq_bn_backward_reduce_arg.restype = ctypes.c_int
-_lib.bq_sa_bwd_supported.argtypes = [_i, _i, _i, _i, _i]
-_lib.bq_sa_bwd_supported.restype = ctypes.c_int
-_lib.bq_sa_bwd_workgroups.argtypes = [_l, _i, _i, _i, _i]
-_lib.bq_sa_bwd_workgroups.restype = ctypes.c_int
-_lib.bq_sa_bwd_fused.argtypes = [_vp] * 13 + [_l, _i, _i, _i, _i, _i, _i, _i, _vp]
-_lib.bq_sa_bwd_fused.restype = ctypes.c_int
-_lib.bq_sa_bwd_fused_x.argtypes = [_vp] * 15 + [_l, _i, _i, _i, _i, _i, _i, _i, _vp]
-_lib.bq_sa_bwd_fused_x.restype = ctypes.c_int
-_lib.bq_sa_bwd_fused_xr.argtypes = [_vp] * 19 + [_l, _i, _i, _i, _i, _i, _i, _i, _vp]
-_lib.bq_sa_bwd_fused_xr.restype = ctypes.c_int
-_lib.bq_sa_bwd_reduce_supported.argtypes = [_i, _i, _i, _i]
-_lib.bq_sa_bwd_reduce_supported.restype = ctypes.c_int
 # a layer's fused backward can also sum the PREVIOUS layer's dbeta / dgamma (its dOut and its pre-activation are both in the pass:
 # "the BatchNorm reduce in the epilogue of the next layer's dX GEMM").  Built, parity-green, and SLOWER: the second barrier per
 # tile, the table reads and 32 more live registers per lane cost the fused kernels more than the eight reduction launches they
 # replace (c2 7.72 / 7.77 -> 7.91 / 7.95 ms, c3 33.50 -> 33.41 inside the noise).  Off; BQ_CARRY_REDUCE=1 switches it on.
 CARRY_REDUCE = [os.environ.get("BQ_CARRY_REDUCE", "0") == "1"]
-_lib.bq_pwconv_bn_fwd_x.argtypes = [_vp, _vp, _vp, _l, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp,
-                                    _vp, _vp, _vp, _vp, _vp]
-_lib.bq_pwconv_bn_fwd_x.restype = ctypes.c_int
 # SharedMLP layers hand their stored pre-activation to the next layer, which applies BatchNorm + ReLU on load (no bn_apply pass,
 # no activation tensor between two convolutions); off / BQ_DEFER_BN=0: every layer writes its activation
 DEFER_BN = [os.environ.get("BQ_DEFER_BN", "1") != "0"]
@@ -1656,15 +1477,9 @@ def sa_bwd_fused(x, y_raw, dout, arg, w_pad, stats, dgb, S, relu, pool, need_dx,
 #  -- the layer output's error drops to one bf16 rounding, the 200-step convergence gap to fp32 does NOT
 # close (+7.2 % against +3.3 % with the stored pre-activation, fp32's own spread 13 %) and the c3 step costs 1.3 ms more
 FP32_PREACT = [False]
-_lib.bq_pwconv_bn_apply.argtypes = [_vp, _l, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]
-_lib.bq_pwconv_bn_apply.restype = ctypes.c_int
 
 
 # ---- LM head + label-smoothed cross entropy (csrc/lmhead.hip + the cross-entropy epilogue of csrc/gemm.hip) -----------
-_lib.bq_lmhead_ce_combine.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]
-_lib.bq_lmhead_ce_combine.restype = ctypes.c_int
-_lib.bq_lmhead_ce_dlogits.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]
-_lib.bq_lmhead_ce_dlogits.restype = ctypes.c_int
 
 
 def lmhead_ce_fwd(h, w, bias_pad, target, V, label_smoothing):
@@ -1704,27 +1519,8 @@ _DET_TERM = {"vote_xyz": 0, "objectness_scores": 1, "center": 2, "heading_scores
              "size_scores": 5, "size_residuals_normalized": 6, "sem_cls_scores": 7}
 
 
-class _DetLossDesc(ctypes.Structure):
-    _fields_ = ([(n, _vp) for n in (
-        "seed_xyz", "vote_xyz", "aggregated_vote_xyz", "objectness_scores", "center", "heading_scores",
-        "heading_residuals_normalized", "size_scores", "size_residuals_normalized", "sem_cls_scores", "seed_inds", "vote_label",
-        "vote_label_mask", "center_label", "box_label_mask", "heading_class_label", "size_class_label", "sem_cls_label",
-        "heading_residual_label", "size_residual_label", "mean_size_arr", "terms", "objectness_label", "objectness_mask",
-        "object_assignment", "g_vote_xyz", "g_objectness_scores", "g_center", "g_heading_scores",
-        "g_heading_residuals_normalized", "g_size_scores", "g_size_residuals_normalized", "g_sem_cls_scores", "scratch")]
-        + [(n, _i) for n in ("B", "S", "VF", "N", "K", "G", "NH", "NS", "NC", "cl_ld", "seed_inds_i64")]
-        + [("ld_" + n, _i) for n in _DET_SCORES]
-        + [(n, _f) for n in ("near_threshold", "far_threshold", "objectness_weight_neg", "objectness_weight_pos")])
-
-
-class _DetLossSeg(ctypes.Structure):
-    _fields_ = [("g", _vp), ("out", _vp), ("rows", _i), ("width", _i), ("ld", _i), ("term", _i)]
-
-
-_lib.bq_det_loss_fwd.argtypes = [ctypes.POINTER(_DetLossDesc), _vp]
-_lib.bq_det_loss_fwd.restype = ctypes.c_int
-_lib.bq_det_loss_bwd.argtypes = [ctypes.POINTER(_DetLossSeg), _i, _vp, _vp]
-_lib.bq_det_loss_bwd.restype = ctypes.c_int
+_DetLossDesc = _cabi.STRUCTS["bq_det_loss_desc"]
+_DetLossSeg = _cabi.STRUCTS["bq_det_loss_seg"]
 
 
 def det_score_ld(v, K):
@@ -1856,14 +1652,6 @@ def det_loss_bwd(grads, upstream, packing=None):
 
 # ---- deterministic scatter gradients through an inverted index (csrc/invert.hip) ---------------------------------------------
 DETERMINISTIC_SCATTER = [True]
-_lib.bq_invert_index_workspace_bytes.argtypes = [_l]
-_lib.bq_invert_index_workspace_bytes.restype = ctypes.c_size_t
-_lib.bq_invert_index.argtypes = [_vp, _i, _l, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]
-_lib.bq_invert_index.restype = ctypes.c_int
-_lib.bq_group_concat_pm_grad_gather.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]
-_lib.bq_group_concat_pm_grad_gather.restype = ctypes.c_int
-_lib.bq_three_interpolate_grad_gather.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
-_lib.bq_three_interpolate_grad_gather.restype = ctypes.c_int
 
 
 def invert_index(idx, N):
@@ -1919,20 +1707,10 @@ def three_interpolate_grad_gather(grad_out, inv, weight, m):
 
 
 # ---- eval-mode SharedMLP of one detector module in one launch (csrc/mlp_eval.hip) ----------------------------------------
-class _MlpEvalLayer(ctypes.Structure):
-    _fields_ = [("w", _vp), ("gamma", _vp), ("beta", _vp), ("mean", _vp), ("var", _vp), ("bias", _vp), ("eps", _f),
-                ("n", _i), ("ldw", _i), ("relu", _i)]
+_MlpEvalLayer = _cabi.STRUCTS["bq_mlp_eval_layer"]
+_MlpEvalDesc = _cabi.STRUCTS["bq_mlp_eval_desc"]
 
 
-class _MlpEvalDesc(ctypes.Structure):
-    _fields_ = [("xyz", _vp), ("new_xyz", _vp), ("feats", _vp), ("f_bs", _l), ("f_rs", _l), ("idx", _vp),
-                ("B", _i), ("C", _i), ("N", _i), ("M", _i), ("S", _i), ("radius", _f), ("normalize", _i),
-                ("x", _vp), ("ldx", _l), ("K", _i), ("R", _l), ("n_layers", _i), ("layers", _MlpEvalLayer * 3),
-                ("has_tail", _i), ("tail", _MlpEvalLayer), ("out", _vp), ("pool", _i)]
-
-
-_lib.bq_mlp_eval.argtypes = [ctypes.POINTER(_MlpEvalDesc), _vp]
-_lib.bq_mlp_eval.restype = ctypes.c_int
 MLP_EVAL_KMAX = 512     # input channels (rounded up to 32) the kernel stages
 MLP_EVAL_S = (16, 32, 64)
 
