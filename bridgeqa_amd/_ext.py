@@ -31,6 +31,7 @@ if _lib.bq_abi_version() != ABI_VERSION:
     raise ImportError("bridgeqa_amd: libbqhip.so ABI %d != %d (stale library: python -m bridgeqa_amd.build --force)"
                       % (_lib.bq_abi_version(), ABI_VERSION))
 _cabi.bind(_lib)
+_cabi.bind(_lib, _cabi.ADDITIVE_PROTOS)
 
 # ---- the deterministic training mode (bridgeqa_amd.set_deterministic) ------------------------------------------------------------
 # Every site of the training path where float atomics from several workgroups met on one address, the entry point that takes it in
@@ -485,6 +486,84 @@ def attn_decode_cross(q, kv, scale, mask_log2=None, out=None):
                                          kv.stride(0), kv.stride(1), kv.stride(3), out.stride(0), out.stride(2), float(scale),
                                          _stream()), "attn_decode_cross")
     return out
+
+
+# ---- the LSTM recurrence of the question branch (csrc/lstm.hip) ---------------------------------------------------------------
+LSTM_HIDDEN = (128, 256)   # hidden sizes lstm_fwd_kernel / lstm_bwd_kernel are built for
+LSTM_CALLS = [0, 0]        # launches of lstm_fwd / lstm_bwd so far (tests assert the route taken)
+
+
+def _lstm_operand(t, shape, name, dtype=torch.float32):
+    if not t.is_cuda:
+        raise RuntimeError("%s: CPU not supported" % name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s must be a %s tensor of shape %s, got %s %s" % (name, str(dtype).replace("torch.", ""),
+                                                                            tuple(shape), t.dtype, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise RuntimeError("%s must be a contiguous tensor" % name)
+
+
+def _lstm_hidden(H, what):
+    if H not in LSTM_HIDDEN:
+        raise RuntimeError("%s: hidden size %d is not built (supported: %s)" % (what, H, ", ".join(map(str, LSTM_HIDDEN))))
+
+
+def lstm_fwd(gx, wt, lens, t_out, reverse=False, save=False):
+    """the recurrence of one LSTM layer and direction.  gx: f32 (B, T, 4H) = x W_ih^T + b_ih + b_hh (gate order i f g o); wt: f32
+    (H, 4H) = W_hh^T; lens: int32 (B) on the device, clamped to [0, t_out] by the kernel; t_out <= T.  Returns y (B, t_out, H)
+    with rows t >= lens[b] zero, h_last (B, H), and with `save` the post-activation gates (B, t_out, 4H) and cell states
+    (B, t_out, H) that lstm_bwd reads (else None, None).  Every check is made before the launch."""
+    for x, n in ((gx, "gx"), (wt, "wt"), (lens, "lens")):
+        if not x.is_cuda:
+            raise RuntimeError("lstm_fwd: %s: CPU not supported" % n)
+    if gx.dim() != 3 or gx.shape[2] % 4:
+        raise RuntimeError("lstm_fwd: gx must be (B, T, 4H)")
+    B, T, H = gx.shape[0], gx.shape[1], gx.shape[2] // 4
+    _lstm_hidden(H, "lstm_fwd")
+    _lstm_operand(gx, (B, T, 4 * H), "lstm_fwd: gx")
+    _lstm_operand(wt, (H, 4 * H), "lstm_fwd: wt")
+    _lstm_operand(lens, (B,), "lstm_fwd: lens", torch.int32)
+    t_out = int(t_out)
+    if not 0 <= t_out <= T:
+        raise RuntimeError("lstm_fwd: t_out %d outside [0, T = %d]" % (t_out, T))
+    _same_device(gx, wt, lens)
+    with torch.cuda.device(gx.device):
+        y = torch.empty(B, t_out, H, dtype=torch.float32, device=gx.device)
+        h_last = torch.empty(B, H, dtype=torch.float32, device=gx.device)
+        gates = torch.empty(B, t_out, 4 * H, dtype=torch.float32, device=gx.device) if save else None
+        cells = torch.empty(B, t_out, H, dtype=torch.float32, device=gx.device) if save else None
+        LSTM_CALLS[0] += 1
+        _check(_lib.bq_lstm_fwd(_p(gx), _p(wt), _p(lens), _p(y), _p(h_last), _p(gates), _p(cells), B, T, t_out, H,
+                                int(bool(reverse)), _stream()), "lstm_fwd")
+    return y, h_last, gates, cells
+
+
+def lstm_bwd(dy, dh_last, gates, cells, w_hh, lens, reverse=False):
+    """gradient of the pre-activation gates.  dy: f32 (B, t_out, H) or None; dh_last: f32 (B, H) or None; gates / cells as
+    lstm_fwd saved them; w_hh: f32 (4H, H) as nn.LSTM holds it; lens as in lstm_fwd.  Returns dgx (B, t_out, 4H) with rows
+    t >= lens[b] zero."""
+    for x, n in ((dy, "dy"), (dh_last, "dh_last"), (gates, "gates"), (cells, "cells"), (w_hh, "w_hh"), (lens, "lens")):
+        if x is not None and not x.is_cuda:
+            raise RuntimeError("lstm_bwd: %s: CPU not supported" % n)
+    if cells.dim() != 3:
+        raise RuntimeError("lstm_bwd: cells must be (B, t_out, H)")
+    B, t_out, H = cells.shape
+    _lstm_hidden(H, "lstm_bwd")
+    _lstm_operand(cells, (B, t_out, H), "lstm_bwd: cells")
+    _lstm_operand(gates, (B, t_out, 4 * H), "lstm_bwd: gates")
+    _lstm_operand(w_hh, (4 * H, H), "lstm_bwd: w_hh")
+    _lstm_operand(lens, (B,), "lstm_bwd: lens", torch.int32)
+    if dy is not None:
+        _lstm_operand(dy, (B, t_out, H), "lstm_bwd: dy")
+    if dh_last is not None:
+        _lstm_operand(dh_last, (B, H), "lstm_bwd: dh_last")
+    _same_device(cells, gates, w_hh, lens, *[x for x in (dy, dh_last) if x is not None])
+    with torch.cuda.device(cells.device):
+        dgx = torch.empty(B, t_out, 4 * H, dtype=torch.float32, device=cells.device)
+        LSTM_CALLS[1] += 1
+        _check(_lib.bq_lstm_bwd(_p(dy), _p(dh_last), _p(gates), _p(cells), _p(w_hh), _p(lens), _p(dgx), B, t_out, H,
+                                int(bool(reverse)), _stream()), "lstm_bwd")
+    return dgx
 
 
 # ---- attention of answer ranking: candidate sequences sharing their question's K / V (csrc/attn_rank.hip) -------------------------

@@ -286,7 +286,9 @@ class GraphedRunner(object):
     # ---- what can be replayed --------------------------------------------------------------------------------------
     def usable(self, data_dict):
         m = self.model
-        return (m.training and torch.is_grad_enabled() and getattr(m, "use_blip", False) and "images" in data_dict
+        # (a model with the stage-1 question branch is never replayed: no captured graph holds that branch)
+        return (m.training and torch.is_grad_enabled() and getattr(m, "use_blip", False)
+                and not getattr(m, "lang_branch", False) and "images" in data_dict
                 and torch.is_tensor(data_dict.get("point_clouds")) and data_dict["point_clouds"].is_cuda
                 and isinstance(data_dict.get("question"), dict) and isinstance(data_dict.get("answer"), dict)
                 and data_dict.get("phase", "train") == "train" and ops.compute_dtype() == torch.bfloat16)

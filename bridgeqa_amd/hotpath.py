@@ -6,15 +6,22 @@ object_feat_linear.*, blip_model.*.
 Round 2 widened it to the rest of the VQA branch: the language-classification head and the
 reference-object head that follow the fusion (qa_module.py:735-754 over the modules of :234-249: lang_cls, object_cls,
 linear_blip_to_object, dec_list_qo; enc_list_o exists for state-dict parity only -- the reference never calls it),
-switched on by the reference's own flags use_lang_cls / use_reference (default off, as in ScanQA.__init__).  The
-non-BLIP branch (LSTM language module, MCAN fusion backbone, AttFlat heads: qa_module.py:496-590) stays out.
+switched on by the reference's own flags use_lang_cls / use_reference (default off, as in ScanQA.__init__).
+
+The non-BLIP question branch of the stage-1 ("DET") recipe (qa_module.py:493-590: LSTM language module, lang_feat_linear,
+MCAN_ED fusion backbone, two AttFlat heads, fusion_norm, lang_cls / object_cls / answer_cls) is built by
+ScanQAHotPath(use_blip=False, lang_branch=True) -- default off: without the argument the module tree, the key set and forward()
+are what they were.  Its only sequential part, the LSTM recurrence, runs on csrc/lstm.hip (lang_module.py); the rest are the
+torch compositions of mcan_module.py.  graphed.enable / pipeline.PhasedTrainStep do not carry this branch: such a model always
+takes the eager forward.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .backbone_module import Pointnet2Backbone
-from .mcan_module import SA, SGA
+from .lang_module import LangModule
+from .mcan_module import MCAN_ED, SA, SGA, AttFlat, LayerNorm
 from .proposal_module import ProposalModule
 from .voting_module import VotingModule
 
@@ -52,14 +59,68 @@ def qa_heads_forward(module, data_dict, object_feat, object_mask, fused_feat, fu
     return data_dict
 
 
+def build_lang_branch(module, hidden_size, num_object_class, num_answers, answer_pdrop=0.3, mcan_num_layers=2, mcan_num_heads=8,
+                      mcan_pdrop=0.1, mcan_flat_mlp_size=512, mcan_flat_glimpses=1, mcan_flat_out_size=1024,
+                      lang_use_bidir=False, lang_num_layers=1, lang_emb_size=300, lang_pdrop=0.1):
+    """registers, on `module`, what ScanQA.__init__ creates without use_blip (qa_module.py:252-330), same names and registration
+    order: object_cls, lang_net, lang_feat_linear, lang_cls, attflat_visual, attflat_lang, answer_cls, fusion_backbone,
+    fusion_norm -- a reference stage-1 checkpoint loads with strict=True"""
+    lang_size = hidden_size * (1 + bool(lang_use_bidir))
+    module.object_cls = nn.Sequential(nn.Linear(hidden_size, hidden_size), nn.GELU(), nn.Dropout(0.1),
+                                      nn.Linear(hidden_size, 1))
+    module.lang_net = LangModule(num_object_class, use_lang_classifier=False, use_bidir=lang_use_bidir,
+                                 num_layers=lang_num_layers, emb_size=lang_emb_size, hidden_size=hidden_size, pdrop=lang_pdrop)
+    module.lang_feat_linear = nn.Sequential(nn.Linear(lang_size, hidden_size), nn.GELU())
+    module.lang_cls = nn.Sequential(nn.Linear(mcan_flat_out_size, hidden_size), nn.GELU(), nn.Dropout(0.1),
+                                    nn.Linear(hidden_size, num_object_class))
+    module.attflat_visual = AttFlat(hidden_size, mcan_flat_mlp_size, mcan_flat_glimpses, mcan_flat_out_size, 0.1)
+    module.attflat_lang = AttFlat(hidden_size, mcan_flat_mlp_size, mcan_flat_glimpses, mcan_flat_out_size, 0.1)
+    module.answer_cls = nn.Sequential(nn.Linear(mcan_flat_out_size, hidden_size), nn.GELU(), nn.Dropout(answer_pdrop),
+                                      nn.Linear(hidden_size, num_answers))
+    module.fusion_backbone = MCAN_ED(hidden_size, num_heads=mcan_num_heads, num_layers=mcan_num_layers, pdrop=mcan_pdrop)
+    module.fusion_norm = LayerNorm(mcan_flat_out_size)
+    return module
+
+
+def lang_branch_forward(module, data_dict, object_feat, object_mask, use_lang_cls, use_reference, use_answer):
+    """qa_module.py:501-587.  data_dict: lang_feat (B, T, emb), lang_len (B), objectness_scores (under use_reference);
+    object_feat (B, K, hidden); object_mask (B, 1, 1, K) bool, True = NOT an object, or None.  Writes lang_out, lang_emb,
+    lang_mask (LangModule), fuse_feat, and cluster_ref / lang_scores / answer_scores under their flags."""
+    data_dict = module.lang_net(data_dict)
+    lang_feat, lang_mask = data_dict["lang_out"], data_dict["lang_mask"]
+    if lang_mask.dim() == 2:
+        lang_mask = lang_mask.unsqueeze(1).unsqueeze(2)
+    lang_feat = module.lang_feat_linear(lang_feat)
+    lang_feat, object_feat = module.fusion_backbone(lang_feat, object_feat, lang_mask, object_mask)
+    if use_reference:
+        conf = object_feat * data_dict["objectness_scores"].max(2)[1].float().unsqueeze(2)
+        data_dict["cluster_ref"] = module.object_cls(conf).squeeze(-1)
+    lang_feat = module.attflat_lang(lang_feat, lang_mask)
+    object_feat = module.attflat_visual(object_feat, object_mask, 0, 100)   # (ScanQA.att_pdrop: 0, no flag in train.py)
+    fuse_feat = module.fusion_norm(lang_feat + object_feat)
+    data_dict["fuse_feat"] = fuse_feat.clone()
+    if use_lang_cls:
+        data_dict["lang_scores"] = module.lang_cls(fuse_feat)
+    if use_answer:
+        data_dict["answer_scores"] = module.answer_cls(fuse_feat)
+    return data_dict
+
+
 class ScanQAHotPath(nn.Module):
     def __init__(self, input_feature_dim=132, num_proposal=256, vote_factor=1, seed_feat_dim=256, proposal_size=128,
                  vote_radius=0.3, vote_nsample=16, hidden_size=256, num_class=18, num_heading_bin=1,
                  num_size_cluster=18, mean_size_arr=None, use_blip=True, blip_kwargs=None, use_lang_cls=False,
-                 use_reference=False, qa_heads=None, mcan_num_layers=2, mcan_num_heads=8, mcan_pdrop=0.1):
+                 use_reference=False, qa_heads=None, mcan_num_layers=2, mcan_num_heads=8, mcan_pdrop=0.1, lang_branch=False,
+                 num_answers=None, answer_pdrop=0.3, mcan_flat_mlp_size=512, mcan_flat_glimpses=1, mcan_flat_out_size=1024,
+                 lang_use_bidir=False, lang_num_layers=1, lang_emb_size=300, lang_pdrop=0.1, use_answer=False,
+                 use_object_mask=False):
         """use_lang_cls / use_reference: ScanQA's flags for the two heads after the fusion; qa_heads: create their
         modules (default: iff one of the flags is set; ScanQA itself always creates them under use_blip -- pass True to
-        load a reference checkpoint with strict=True)"""
+        load a reference checkpoint with strict=True).
+        lang_branch (with use_blip=False only): the stage-1 question branch, qa_module.py:252-330 / 493-590, with ScanQA's
+        arguments of that branch and its defaults (num_answers has none and must be given); use_lang_cls / use_reference /
+        use_answer then select lang_scores / cluster_ref / answer_scores.  use_object_mask=False attends over all proposals
+        (the reference itself fails on that setting, qa_module.py:471-473; scripts/train.py sets it unless --no_object_mask)."""
         super().__init__()
         if mean_size_arr is None:
             mean_size_arr = np.ones((num_size_cluster, 3))
@@ -80,6 +141,17 @@ class ScanQAHotPath(nn.Module):
             if qa_heads if qa_heads is not None else (use_lang_cls or use_reference):
                 build_qa_heads(self, hidden_size, self.blip_model.text_encoder.config.hidden_size, num_class,
                                mcan_num_layers, mcan_num_heads, mcan_pdrop)
+        if lang_branch:
+            if use_blip:
+                raise ValueError("lang_branch is the question branch of use_blip=False (stage 1)")
+            if num_answers is None:
+                raise ValueError("lang_branch needs num_answers (the width of answer_cls)")
+            self.lang_branch = True
+            self.use_lang_cls, self.use_reference, self.use_answer = use_lang_cls, use_reference, use_answer
+            self.use_object_mask = use_object_mask
+            build_lang_branch(self, hidden_size, num_class, num_answers, answer_pdrop, mcan_num_layers, mcan_num_heads,
+                              mcan_pdrop, mcan_flat_mlp_size, mcan_flat_glimpses, mcan_flat_out_size, lang_use_bidir,
+                              lang_num_layers, lang_emb_size, lang_pdrop)
 
     def detect(self, data_dict):
         data_dict = self.detection_backbone(data_dict)
@@ -130,6 +202,15 @@ class ScanQAHotPath(nn.Module):
                              data_dict["fused_mask"], self.use_lang_cls, self.use_reference)
         return data_dict
 
+    def question_branch(self, data_dict):
+        """the stage-1 question branch over the detector's proposals (qa_module.py:466-474, 493-590); reads lang_feat /
+        lang_len beside the detector outputs"""
+        object_mask = None
+        if self.use_object_mask:
+            object_mask = (~data_dict["bbox_mask"].bool().detach()).unsqueeze(1).unsqueeze(2)  # True = not an object
+        return lang_branch_forward(self, data_dict, data_dict["object_feat"], object_mask, self.use_lang_cls,
+                                   self.use_reference, self.use_answer)
+
     def forward(self, data_dict):
         """data_dict: point_clouds (B,N,3+C); with use_blip also images (B,V,3,H,W), question / answer
         (token dicts or strings).  Adds the detector outputs and, with BLIP, `blip_loss`, `fused_feat`."""
@@ -154,5 +235,7 @@ class ScanQAHotPath(nn.Module):
         else:
             data_dict = self.detect_objects(data_dict)
         if not self.use_blip:
+            if getattr(self, "lang_branch", False):
+                return self.question_branch(data_dict)
             return data_dict
         return self.fuse(data_dict, image_embeds)

@@ -1,12 +1,12 @@
-"""MCAN blocks used by the reference-object head of ScanQA's VQA branch -- mirror of the reference's
-models/mcan_module.py (FC :18-43, MLP :46-54, LayerNorm :57-69, MHAtt :138-224, FFN :229-245, SA :250-273, SGA :278-311)
-with its class names, constructor arguments, forward signatures and state-dict keys (linear_v / linear_k / linear_q /
+"""MCAN blocks used by the reference-object head of ScanQA's VQA branch and by the stage-1 question branch -- mirror of the
+reference's models/mcan_module.py (FC :18-43, MLP :46-54, LayerNorm :57-69, AttFlat :74-133, MHAtt :138-224, FFN :229-245,
+SA :250-273, SGA :278-311, MCAN_E :316-327, MCAN_ED :330-355) with its class names, constructor arguments, forward signatures and state-dict keys (linear_v / linear_k / linear_q /
 linear_merge, mlp.fc.linear, mlp.linear, a_2 / b_2), so reference checkpoints load with strict=True.
 
 SURVEY.md §8f rank 1 ("ScanQA.forward glue"): these blocks sit on the CALLER side of the hot path -- 2 layers over 256
 proposals x 256 channels against 20 question states, < 0.1 % of the step's flop -- so they run on torch ops (fp32), no
-kernels of their own.  AttFlat and the MCAN_E / MCAN_ED stacks belong to the non-BLIP branch (qa_module.py:496-590) and are
-not part of this path.
+kernels of their own.  AttFlat and the MCAN_E / MCAN_ED stacks belong to the non-BLIP question branch (qa_module.py:496-590;
+hotpath.ScanQAHotPath(use_blip=False, lang_branch=True)): torch compositions over the same blocks.
 
 Reference quirks kept on purpose (parity, not opinion):
   * LayerNorm divides by (std + eps) with the UNBIASED standard deviation (torch.std), not sqrt(var + eps);
@@ -130,3 +130,52 @@ class SGA(nn.Module):
         x = self.norm1(x + self.dropout1(self.mhatt1(x, x, x, x_mask)))
         x = self.norm2(x + self.dropout2(self.mhatt2(y, y, x, y_mask, att_pdrop, att_drop_topk)))
         return self.norm3(x + self.dropout3(self.ffn(x)))
+
+
+class AttFlat(nn.Module):
+    """attention pooling over the tokens (mcan_module.py:74-133): softmax over MLP(x) per glimpse, masked keys at -1e9, the
+    glimpses' weighted sums concatenated and merged.  x_mask (B, 1, 1, N) bool, True = hide.  The att_pdrop > 0 top-k masking
+    has no flag in scripts/train.py (ScanQA's att_pdrop stays 0) and is not carried."""
+
+    def __init__(self, hidden_size, flat_mlp_size=512, flat_glimpses=1, flat_out_size=1024, pdrop=0.1):
+        super().__init__()
+        self.mlp = MLP(in_size=hidden_size, mid_size=flat_mlp_size, out_size=flat_glimpses, pdrop=pdrop, use_gelu=True)
+        self.flat_glimpses = flat_glimpses
+        self.linear_merge = nn.Linear(hidden_size * flat_glimpses, flat_out_size)
+
+    def forward(self, x, x_mask, att_pdrop=0, att_drop_topk=100):
+        if att_pdrop > 0:
+            raise NotImplementedError("AttFlat: att_pdrop > 0 (top-k score masking) is not supported")
+        att = self.mlp(x)
+        if x_mask is not None:
+            att = att.masked_fill(x_mask.squeeze(1).squeeze(1).unsqueeze(2), -1e9)
+        att = F.softmax(att, dim=1)
+        x_atted = torch.cat([torch.sum(att[:, :, i:i + 1] * x, dim=1) for i in range(self.flat_glimpses)], dim=1)
+        return self.linear_merge(x_atted)
+
+
+class MCAN_E(nn.Module):
+    def __init__(self, hidden_size, num_heads=8, num_layers=6, pdrop=0.1):
+        super().__init__()
+        self.enc_list = nn.ModuleList([SA(hidden_size, num_heads, pdrop) for _ in range(num_layers)])
+
+    def forward(self, x, x_mask):
+        for enc in self.enc_list:
+            x = enc(x, x_mask)
+        return x
+
+
+class MCAN_ED(nn.Module):
+    """encoder over x (self-attention), then decoder over y guided by the encoded x (mcan_module.py:330-355)"""
+
+    def __init__(self, hidden_size, num_heads=8, num_layers=6, pdrop=0.1):
+        super().__init__()
+        self.enc_list = nn.ModuleList([SA(hidden_size, num_heads, pdrop) for _ in range(num_layers)])
+        self.dec_list = nn.ModuleList([SGA(hidden_size, num_heads, pdrop) for _ in range(num_layers)])
+
+    def forward(self, x, y, x_mask, y_mask, att_pdrop=0, att_drop_topk=100):
+        for enc in self.enc_list:
+            x = enc(x, x_mask)
+        for dec in self.dec_list:
+            y = dec(y, x, y_mask, x_mask, att_pdrop, att_drop_topk)
+        return x, y

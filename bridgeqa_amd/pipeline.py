@@ -85,6 +85,9 @@ class PhasedTrainStep(object):
         text_prologue: the token-only head of the fusion (question / answer embeddings, BLIP_VQA3D.prepare_text) and its
         backward as phases of their own on the detector stream, beside the image encoder / the image backward, instead of on
         the critical chain (~50 launches of 5 us)."""
+        if getattr(model, "lang_branch", False):
+            raise ValueError("PhasedTrainStep does not schedule the stage-1 question branch (lang_branch=True): run the "
+                             "eager forward, model(data_dict)")
         self.model, self.batch, self.det_loss, self.fusion_loss = model, batch, det_loss, fusion_loss
         self.opt, self.grad_hook = optimizer, grad_hook
         if prefetch_geometry and next_batch is None:

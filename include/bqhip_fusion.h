@@ -10,6 +10,7 @@
 #ifndef BQHIP_FUSION_H
 #define BQHIP_FUSION_H
 #include "bqhip.h"
+#include "bqhip_lstm.h" /* bq_lstm_fwd / bq_lstm_bwd: additive to ABI 6 */
 
 #ifdef __cplusplus
 extern "C" {
