@@ -15,8 +15,10 @@
 // caller's weights -- scripts/train.py:97-103 -- and the x10 stay ordinary autograd arithmetic on eight scalars).
 //
 // Arithmetic: fp32 throughout, formulas in the reference's form (log-softmax as x - max - log(sum exp(x - max)),
-// Huber as 0.5 q^2 + delta (|e| - q)); reductions in a different order than torch's => compared at 1e-5 relative
-// (tests/test_detloss_gpu.py against loss_helper.py and tests/golden/det_loss.npz).  torch.min's first-index tie rule kept.
+// Huber as 0.5 q^2 + delta (|e| - q)); reductions in a different order than torch's => every term, ratio and gradient
+// element is held to the fp64 bound derived from the roundings below in tests/detloss_ref.py, labels and picks exactly
+// (tests/test_detloss_bound_gpu.py; tests/test_detloss_gpu.py against loss_helper.py and tests/golden/det_loss.npz).
+// torch.min's first-index tie rule kept.
 #include "bq_common.h"
 #include "bqhip_fusion.h"
 

@@ -2,7 +2,9 @@
 gradient in two launches against (a) the reference's own lib/loss_helper.py through tests/golden/det_loss.npz and (b) the
 torch composition of bridgeqa_amd/loss_helper.py -- every term, the labels / masks / assignments exactly, the gradient
 w.r.t. every network output -- in the three layouts the kernel reads: separate contiguous tensors, separate channel slices
-(graphed.wrap_loss' leaves), slices of one head output inside the autograd graph (the training step)."""
+(graphed.wrap_loss' leaves), slices of one head output inside the autograd graph (the training step).
+The elementwise check -- every label and pick exactly, every term and gradient element within a derived fp64 bound, more shapes,
+degenerate batches and exact ties -- lives in tests/test_detloss_bound_gpu.py over tests/detloss_ref.py."""
 import types
 
 import numpy as np
