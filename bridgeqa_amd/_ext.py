@@ -1002,7 +1002,8 @@ def box_point_count(points, center, size, heading, cap=0):
 
 
 def nms(box, score, thresh, cls=None, valid=None, old_type=False, same_cls=False):
-    """box f32 (B, K, 6) axis-aligned extents, score f32 (B, K), cls i32 (B, K), valid u8 / bool (B, K) -> bool (B, K)"""
+    """box f32 (B, K, 6) axis-aligned extents, score f32 (B, K), cls i32 (B, K), valid u8 / bool (B, K) -> bool (B, K);
+    thresh is compared as the Python float (a double), NaN scores are visited first, ties in index order"""
     if not box.is_cuda:
         raise RuntimeError("box: CPU not supported")
     B, K = score.shape
@@ -1011,8 +1012,8 @@ def nms(box, score, thresh, cls=None, valid=None, old_type=False, same_cls=False
     valid = valid.contiguous().to(torch.uint8) if valid is not None else None
     with torch.cuda.device(box.device):
         keep = torch.empty(B, K, dtype=torch.uint8, device=box.device)
-        _check(_lib.bq_nms(_p(box), _p(score), _p(cls), _p(valid), _p(keep), B, K, float(thresh), int(bool(old_type)),
-                           int(bool(same_cls)), _stream()), "nms")
+        _check(_lib.bq_nms_f64(_p(box), _p(score), _p(cls), _p(valid), _p(keep), B, K, float(thresh), int(bool(old_type)),
+                               int(bool(same_cls)), _stream()), "nms")
     return keep.bool()
 
 

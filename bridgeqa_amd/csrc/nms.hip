@@ -10,9 +10,10 @@ namespace bq {
 
 // ---- points inside an oriented box ------------------------------------------------------------------------------------
 // box (b, k): centre c, size (l, w, h), heading t; corners = roty(t) . local + c (box_util.py:282-300), so a point p is inside
-// iff local = roty(t)^T (p - c) has |x| <= l/2, |y| <= w/2, |z| <= h/2 (the closed box = the convex hull of the corners,
-// which is what the reference's in-hull test decides).  One workgroup per (box, scene); the scene's points (xyz at the
-// head of rows of `ld` floats) stream through; per-wave ballot counts.
+// iff local = roty(t)^T (p - c) has |x| <= |l|/2, |y| <= |w|/2, |z| <= |h|/2 (the closed box = the convex hull of the corners,
+// which is what the reference's in-hull test decides; a negative size component mirrors the corners and spans the same hull,
+// a zero one leaves the points ON that plane).  One workgroup per (box, scene); the scene's points (xyz at the head of rows of
+// `ld` floats) stream through; every lane counts its stride, a 64-lane butterfly and four wave partials add up.
 __global__ __launch_bounds__(256) void box_point_count_kernel(const float *__restrict__ pc, const float *__restrict__ center,
                                                              const float *__restrict__ size, const float *__restrict__ heading,
                                                              int *__restrict__ count, int N, int ld, int K, int cap) {
@@ -20,7 +21,7 @@ __global__ __launch_bounds__(256) void box_point_count_kernel(const float *__res
   const int k = blockIdx.x, b = blockIdx.y;
   const float *c = center + ((long)b * K + k) * 3, *sz = size + ((long)b * K + k) * 3;
   const float cx = c[0], cy = c[1], cz = c[2];
-  const float hl = 0.5f * sz[0], hw = 0.5f * sz[1], hh = 0.5f * sz[2];
+  const float hl = fabsf(0.5f * sz[0]), hw = fabsf(0.5f * sz[1]), hh = fabsf(0.5f * sz[2]);
   const float t = heading[(long)b * K + k], ct = cosf(t), st = sinf(t);
   const float *p = pc + (long)b * N * ld;
   int mine = 0;
@@ -46,12 +47,15 @@ __global__ __launch_bounds__(256) void box_point_count_kernel(const float *__res
 // threshold -- overlap = IoU, or (old_type) intersection / the OTHER box's volume; with same_cls only boxes of the picked
 // box's class can be suppressed.  Boxes with valid == 0 (empty boxes removed beforehand) do not take part.
 // box: (B, K, 6) = (x1, y1, z1, x2, y2, z2); for the 2-D variant the caller passes z1 = 0, z2 = 1.  Arithmetic in double,
-// as numpy's.  Ties of the score are visited in increasing index order (numpy's argsort order for ties is unspecified).
+// as numpy's, the threshold a double too (the Python float the reference compares with, not its fp32 rounding).  The visit order
+// is a TOTAL order for any scores: a NaN ranks above every number (numpy's argsort places it last = picked first), numbers in
+// decreasing order (+0 == -0, +-inf as numbers), equal scores and NaNs among themselves in increasing index order (numpy's
+// order for ties is unspecified) -- so the ranks are a permutation of 0..K-1 and every s_order slot is written exactly once.
 constexpr int NMS_MAX_K = 1024;
 
 __global__ __launch_bounds__(256) void nms_kernel(const float *__restrict__ box, const float *__restrict__ score,
                                                   const int *__restrict__ cls, const unsigned char *__restrict__ valid,
-                                                  unsigned char *__restrict__ keep, int K, float thresh, int old_type,
+                                                  unsigned char *__restrict__ keep, int K, double thresh, int old_type,
                                                   int same_cls) {
   __shared__ float s_score[NMS_MAX_K];
   __shared__ short s_order[NMS_MAX_K];
@@ -68,10 +72,12 @@ __global__ __launch_bounds__(256) void nms_kernel(const float *__restrict__ box,
   // rank sort (K <= 1024: K^2 / 256 comparisons per thread): position of i in (score desc, index asc)
   for (int i = t; i < K; i += 256) {
     const float si = s_score[i];
+    const bool ni = si != si;
     int rank = 0;
     for (int j = 0; j < K; ++j) {
       const float sj = s_score[j];
-      rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
+      const bool first = sj != sj ? (!ni || j < i) : (!ni && (sj > si || (sj == si && j < i)));
+      rank += first ? 1 : 0;
     }
     s_order[rank] = (short)i;
   }
@@ -94,7 +100,7 @@ __global__ __launch_bounds__(256) void nms_kernel(const float *__restrict__ box,
         const double inter = l * w * h, vj = (a2 - a1) * (b2 - b1) * (c2 - c1);
         double o = old_type ? inter / vj : inter / (vi + vj - inter);
         if (same_cls && cls && cls[(long)b * K + j] != ci) o = 0.0;
-        if (o > (double)thresh) s_alive[j] = 0;
+        if (o > thresh) s_alive[j] = 0;
       }
       if (t == 0) {
         keep[(long)b * K + i] = 1;
@@ -119,13 +125,19 @@ extern "C" __attribute__((visibility("default"))) int bq_box_point_count(
   return check_launch("box_point_count");
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_nms(
+extern "C" __attribute__((visibility("default"))) int bq_nms_f64(
     const float *box, const float *score, const int *cls, const unsigned char *valid, unsigned char *keep, int B, int K,
-    float thresh, int old_type, int same_cls, void *stream) {
+    double thresh, int old_type, int same_cls, void *stream) {
   BQ_REQUIRE(box && score && keep, BQ_EINVAL, "nms: null pointer");
   BQ_REQUIRE(B > 0 && K > 0 && K <= NMS_MAX_K, BQ_ELIMIT, "nms: K = %d outside 1..%d", K, NMS_MAX_K);
   BQ_REQUIRE(!same_cls || cls, BQ_EINVAL, "nms: same_cls needs the class ids");
   hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, box, score, cls, valid, keep, K, thresh,
                      old_type, same_cls);
   return check_launch("nms");
+}
+
+extern "C" __attribute__((visibility("default"))) int bq_nms(
+    const float *box, const float *score, const int *cls, const unsigned char *valid, unsigned char *keep, int B, int K,
+    float thresh, int old_type, int same_cls, void *stream) {
+  return bq_nms_f64(box, score, cls, valid, keep, B, K, (double)thresh, old_type, same_cls, stream);
 }

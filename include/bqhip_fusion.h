@@ -305,15 +305,21 @@ BQ_API int bq_adamw_multi(const void *table, const void *chunks, int n_chunks, c
  * bq_box_point_count: count[b][k] = number of points of scene b inside box k (remove_empty_box, ap_helper.py:88-100,
  *   whose in-hull test over the 8 corners of utils/box_util.py:282-300 get_3d_box is the closed oriented box):
  *   points f32 (B, N, ld) with xyz first, center / size f32 (B, K, 3) (size = l, w, h), heading f32 (B, K) radians
- *   (rotation `roty`); cap > 0 clamps the count (the caller only compares with 5).
+ *   (rotation `roty`); the box is the closed one of half extents |size| / 2 (a negative component spans the same hull);
+ *   cap > 0 clamps the count (the caller only compares with 5).
  * bq_nms: greedy NMS of every scene (utils/nms.py:40-152 nms_2d_faster / nms_3d_faster / nms_3d_faster_samecls): box
  *   f32 (B, K, 6) = (x1, y1, z1, x2, y2, z2) (2-D: z1 = 0, z2 = 1), score f32 (B, K), cls i32 (B, K) or NULL, valid u8
  *   (B, K) or NULL (boxes left out), keep u8 (B, K) out; old_type: overlap = intersection / the other box's volume
- *   instead of IoU; same_cls: only boxes of the picked box's class are suppressed.  K <= 1024.  Double arithmetic. */
+ *   instead of IoU; same_cls: only boxes of the picked box's class are suppressed.  K <= 1024.  Double arithmetic.
+ *   Visit order: NaN scores first, then score descending (+0 == -0), equal scores and NaNs by increasing index.
+ * bq_nms_f64 (additive to ABI 6): the same with the threshold a double, compared as such -- the Python float the
+ *   reference compares its float64 overlaps with; bq_nms forwards (double)thresh, i.e. the fp32 rounding of it. */
 BQ_API int bq_box_point_count(const float *points, const float *center, const float *size, const float *heading, int *count,
                               int B, int N, int ld, int K, int cap, void *stream);
 BQ_API int bq_nms(const float *box, const float *score, const int *cls, const unsigned char *valid, unsigned char *keep,
                   int B, int K, float thresh, int old_type, int same_cls, void *stream);
+BQ_API int bq_nms_f64(const float *box, const float *score, const int *cls, const unsigned char *valid, unsigned char *keep,
+                      int B, int K, double thresh, int old_type, int same_cls, void *stream);
 
 /* ---- detection mAP (csrc/ap_eval.hip) ----------------------------------------------------------------------------
  * Replaces the host loops of utils/eval_det.py:57-141 eval_det_cls / :4-35 voc_ap (non-07 metric) over

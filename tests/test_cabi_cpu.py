@@ -28,7 +28,7 @@ def _declared():
 
 def test_every_declaration_is_parsed_and_bound():
     names = _declared()
-    assert len(names) == len(set(names)) == len(_cabi.PROTOS) == 96
+    assert len(names) == len(set(names)) == len(_cabi.PROTOS) == 97
     assert set(names) == set(_cabi.PROTOS)
     # bind() sets both attributes on every name, also where the value equals ctypes' default
     fake = types.SimpleNamespace(**{n: types.SimpleNamespace() for n in names})
@@ -76,6 +76,8 @@ def test_hand_written_pins():
     assert P["bq_drop_add_ln_bwd_det_slab_floats"] == (_l, [_i, _i, _i])
     assert P["bq_last_error"] == (ctypes.c_char_p, [])
     assert P["bq_ap_match"][1][5] is _vp        # const double *thresholds: a plain pointer like every other
+    assert P["bq_nms"] == (_i, [_vp] * 5 + [_i, _i, _f, _i, _i, _vp])
+    assert P["bq_nms_f64"] == (_i, [_vp] * 5 + [_i, _i, ctypes.c_double, _i, _i, _vp])      # the threshold by value, a double
     assert D["BQ_GEMM_DET"] == 16 and D["BQ_EINVAL"] == -1 and D["BQHIP_ABI_VERSION"] == 6
 
 
