@@ -566,6 +566,90 @@ def lstm_bwd(dy, dh_last, gates, cells, w_hh, lens, reverse=False):
     return dgx
 
 
+# ---- training-scene preparation: sample, augment, vote labels (csrc/scene_prep.hip, include/bqhip_scene.h) -----------------------
+SCENE_XF = _cabi.ADDITIVE_DEFINES["BQ_SCENE_XF"]             # doubles per sample: flips, Rx, Ry, Rz, t, Rz Ry Rx
+SCENE_ENTRY = _cabi.ADDITIVE_DEFINES["BQ_SCENE_ENTRY"]       # unsigneds per (sample, instance id) of the min / max / first table
+SCENE_MAX_IDS = _cabi.ADDITIVE_DEFINES["BQ_SCENE_MAX_IDS"]   # instance ids 0 .. SCENE_MAX_IDS - 1
+SCENE_CALLS = [0, 0, 0]    # launches of scene_boxes / scene_sample / scene_votes so far (tests count launches per batch)
+
+
+def _scene_operand(t, shape, dtype, name):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError("scene_prep: %s: CPU not supported (a device tensor is needed)" % name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise RuntimeError("scene_prep: %s must be a %s tensor of shape %s, got %s %s"
+                           % (name, str(dtype).replace("torch.", ""), tuple(shape), t.dtype, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise RuntimeError("scene_prep: %s must be a contiguous tensor" % name)
+
+
+def scene_prep(store, scene, object_id, choices, xf, out, table, augment=True, check=False):
+    """one batch of training scenes in three launches.  store: the device tensors of scene_data.SceneStore (rows (sum P, D) f32,
+    inst / sem (sum P) i32, row_base (S + 1) i64, boxes (S, G, 8) f64, num_bbox (S) i32, box_class (S, G) i32, mean_size (NC, 3)
+    f64, votes_sem (L) u8); scene / object_id (B) i32; choices (B, N) i32; xf (B, SCENE_XF) f64 (None without augment); out: every
+    key of scene_data.out_spec, preallocated; table (B, T, SCENE_ENTRY) i32 scratch.  Nothing is allocated and the host does not wait,
+    unless check=True: then choices outside [0, P_scene) and scene indices outside [0, S) raise (one device-to-host read); without
+    it the kernels clamp them.  Every check is made before the first launch."""
+    rows = store.rows
+    if not torch.is_tensor(rows) or not rows.is_cuda or rows.dim() != 2:
+        raise RuntimeError("scene_prep: rows: CPU not supported (a 2-d device tensor is needed)")
+    if not torch.is_tensor(choices) or choices.dim() != 2:
+        raise RuntimeError("scene_prep: choices must be (B, N)")
+    (Ptot, D), (B, N) = rows.shape, choices.shape
+    S, G, NC, L = store.row_base.shape[0] - 1, store.boxes.shape[1], store.mean_size.shape[0], store.votes_sem.shape[0]
+    T = table.shape[1] if torch.is_tensor(table) and table.dim() == 3 else 0
+    for t, shape, dtype, name in ((rows, (Ptot, D), torch.float32, "rows"), (store.inst, (Ptot,), torch.int32, "inst"),
+                                  (store.sem, (Ptot,), torch.int32, "sem"), (store.row_base, (S + 1,), torch.int64, "row_base"),
+                                  (store.boxes, (S, G, 8), torch.float64, "boxes"), (store.num_bbox, (S,), torch.int32, "num_bbox"),
+                                  (store.box_class, (S, G), torch.int32, "box_class"),
+                                  (store.mean_size, (NC, 3), torch.float64, "mean_size"),
+                                  (store.votes_sem, (L,), torch.uint8, "votes_sem"), (scene, (B,), torch.int32, "scene"),
+                                  (object_id, (B,), torch.int32, "object_id"), (choices, (B, N), torch.int32, "choices"),
+                                  (table, (B, T, SCENE_ENTRY), torch.int32, "table")):
+        _scene_operand(t, shape, dtype, name)
+    if augment:
+        _scene_operand(xf, (B, SCENE_XF), torch.float64, "xf")
+    from .scene_data import out_spec   # (imports nothing of this module at load time)
+    spec = out_spec(B, N, D, G, augment)
+    for k, (shape, dtype) in spec.items():
+        if k not in out:
+            raise RuntimeError("scene_prep: out has no %r" % k)
+        _scene_operand(out[k], shape, dtype, "out[%r]" % k)
+    _same_device(rows, store.inst, store.sem, store.row_base, store.boxes, store.num_bbox, store.box_class, store.mean_size,
+                 store.votes_sem, scene, object_id, choices, table, *([xf] if augment else []), *[out[k] for k in spec])
+    if not 1 <= T <= SCENE_MAX_IDS:
+        raise RuntimeError("scene_prep: table holds %d entries per sample (1 .. %d)" % (T, SCENE_MAX_IDS))
+    with torch.cuda.device(rows.device):
+        if check:
+            sl = scene.long()
+            ok_s = (sl >= 0) & (sl < S)
+            sl = sl.clamp(0, S - 1)
+            P = (store.row_base[sl + 1] - store.row_base[sl])[:, None]
+            bad = int((~ok_s).sum()), int(((choices < 0) | (choices >= P)).sum())
+            if bad[0] or bad[1]:
+                raise RuntimeError("scene_prep: %d scene indices outside [0, %d), %d choices outside [0, P of their scene)"
+                                   % (bad[0], S, bad[1]))
+        o = lambda k: _p(out[k]) if k in spec else None
+        st = _stream()
+        SCENE_CALLS[0] += 1
+        _check(_lib.bq_scene_boxes(_p(store.boxes), _p(store.num_bbox), _p(store.box_class), _p(store.mean_size), _p(scene),
+                                   _p(object_id), _p(xf) if augment else None, o("target_bboxes"), o("center_label"),
+                                   o("size_residual_label"), o("heading_residual_label"), o("box_label_mask"),
+                                   o("heading_class_label"), o("size_class_label"), o("sem_cls_label"), o("ref_box_label"),
+                                   o("num_bbox"), o("ref_obj_mask"), o("ref_center_label"), o("ref_size_class_label"),
+                                   o("ref_size_residual_label"), o("flip_x"), o("flip_y"), o("rot_mat"), o("translation"),
+                                   _p(table), S, G, NC, B, T, int(bool(augment)), st), "scene_boxes")
+        SCENE_CALLS[1] += 1
+        _check(_lib.bq_scene_sample(_p(rows), _p(store.inst), _p(store.row_base), _p(scene), _p(choices),
+                                    _p(xf) if augment else None, o("point_clouds"), _p(table), S, B, N, D, T,
+                                    int(bool(augment)), st), "scene_sample")
+        SCENE_CALLS[2] += 1
+        _check(_lib.bq_scene_votes(_p(store.inst), _p(store.sem), _p(store.votes_sem), _p(store.row_base), _p(scene), _p(choices),
+                                   o("point_clouds"), _p(table), o("vote_label"), o("vote_label_mask"), S, B, N, D, T, L, st),
+               "scene_votes")
+    return out
+
+
 # ---- attention of answer ranking: candidate sequences sharing their question's K / V (csrc/attn_rank.hip) -------------------------
 RANK_LMAX = _D["BQ_RANK_LMAX"]       # tokens per sequence attn_rank_self holds in registers
 RANK_QBLOCK = _D["BQ_RANK_QBLOCK"]   # queries a wave of attn_rank_cross carries through one loaded K / V chunk

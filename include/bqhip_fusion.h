@@ -11,6 +11,7 @@
 #define BQHIP_FUSION_H
 #include "bqhip.h"
 #include "bqhip_lstm.h" /* bq_lstm_fwd / bq_lstm_bwd: additive to ABI 6 */
+#include "bqhip_scene.h" /* bq_scene_boxes / bq_scene_sample / bq_scene_votes: additive to ABI 6 */
 
 #ifdef __cplusplus
 extern "C" {
