@@ -10,7 +10,9 @@ __version__ = "0.1.0"
 import os as _os
 
 # ---- the deterministic training mode (README "Environment variables") ------------------------------------------
-# Off by default: every kernel and every bit of a training step are then what they were without the mode.  On: the fusion
+# Off by default: the kernels of a training step are then what they were without the mode, but for one launch -- the LM head's
+# dH, the first gradient of the backward, which every other gradient descends from, is summed in piece order in every mode
+# (fusion_ops._LMHeadCE.backward).  On: the fusion
 # backward's fp32 sums that several workgroups used to add with float atomics (LayerNorm dgamma / dbeta, grouped bias column sums,
 # cut contractions such as the LM head's dH) are stored as per-workgroup partials and folded in a fixed order, so that a step
 # started from the same parameters, buffers, batch and seed (manual_seed) gives the same bits every time.

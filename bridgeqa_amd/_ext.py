@@ -1255,11 +1255,13 @@ def pick_tile(Ni, Nj, q_xc, mid_ok=False):
     return 32
 
 
-def gemm_grouped(problems, flags, epilogue=EPI_NONE, tile=None):
+def gemm_grouped(problems, flags, epilogue=EPI_NONE, tile=None, fixed_order=False):
     """One launch for a list of problems out[j][i] = epilogue(sum_kc P(i,kc) Q(j,kc)) (include/bqhip_fusion.h,
     bq_gemm_bf16).  problems: dicts with P, Q, out (2-D tensors, contiguous last dim) and optional bias (fp32 (Ni,)),
-    out2, aux, colsum (fp32 (Ni,), accumulated).  P: (Ni, Kc), or (Kc, Ni) with GEMM_P_XC; Q likewise over j."""
-    if _det():
+    out2, aux, colsum (fp32 (Ni,), accumulated).  P: (Ni, Kc), or (Kc, Ni) with GEMM_P_XC; Q likewise over j.
+    fixed_order: take the deterministic mode's form (a cut contraction summed in piece order instead of with fp32 atomics)
+    for this launch whatever the mode -- for results that feed further backward passes."""
+    if _det() or fixed_order:
         return _gemm_grouped_det(problems, flags, epilogue, tile)
     return _gemm_grouped_launch(problems, flags, epilogue, tile)
 
@@ -1332,11 +1334,14 @@ def _gemm_grouped_launch(problems, flags, epilogue, tile):
 
 
 def _gemm_grouped_det(problems, flags, epilogue, tile):
-    """gemm_grouped in the deterministic mode (DET_ROUTES): the launch carries GEMM_DET; a cut fp32 contraction (ksplit > 1) runs
-    into per-piece slabs that bq_gemm_splitk_fold_det adds onto `out` in piece order; column sums of a bf16 output are taken
-    after the launch by the grouped fixed-order column sum.  Refuses what has no fixed-order form: stream-K, a cut contraction
-    with column sums."""
-    if STREAMK[0] or STREAMK256[0]:
+    """gemm_grouped in its fixed-order form (DET_ROUTES) -- every launch of the deterministic mode, and in any mode a launch
+    that asks for it (gemm_grouped(fixed_order=True): the LM head's dH): the launch carries GEMM_DET; a cut fp32 contraction
+    (ksplit > 1) runs into per-piece slabs that bq_gemm_splitk_fold_det adds onto `out` in piece order; column sums of a bf16
+    output are taken after the launch by the grouped fixed-order column sum.  Refuses what has no fixed-order form: a cut
+    contraction with column sums and, while the deterministic mode is on, stream-K (a whole step must not mix the two; a single
+    fixed-order launch beside stream-K in the default mode is fine -- stream-K lives in the large-tile kernels, the fixed-order
+    forms in the small-tile one, and the library refuses GEMM_DET on the one tile class where they could meet)."""
+    if _det() and (STREAMK[0] or STREAMK256[0]):
         raise RuntimeError("gemm: stream-K is on (streamk_enable / streamk256_enable) while the deterministic mode is on")
     f32 = bool(flags & GEMM_OUT_F32)
     probs, folds, sums = [], [], []

@@ -11,6 +11,8 @@
 //   m  <- beta1 * m + (1 - beta1) * g            v <- beta2 * v + (1 - beta2) * g * g
 //   p  <- p - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 // with t read from device memory (graph-replay safe: the caller increments it on the stream before this launch).
+// Non-finite gradients behave as under clip_grad_value_ + torch.optim.AdamW: the clamp keeps NaN (as clamp_ does; fmaxf /
+// fminf would return the bound instead) and turns +-inf into +-clip; a NaN gradient element makes its p, m, v and shadow NaN.
 #include <cstdint>
 #include <cstdlib>
 #include "bq_common.h"
@@ -33,6 +35,12 @@ struct AdamWTensor {
 constexpr int ADAMW_CHUNK = BQ_ADAMW_CHUNK;  // elements per workgroup
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+// torch's clamp_: two selects, so that a NaN (for which both comparisons are false) passes through; clip = inf: g untouched
+__device__ __forceinline__ float clamp_keep_nan(float g, float clip) {
+  g = g < -clip ? -clip : g;
+  return g > clip ? clip : g;
+}
 
 // NT: every stream of this kernel is touched exactly once per step -- nontemporal loads / stores keep the 10 GB it
 // moves from evicting the L2 / MALL lines of whatever runs next (default; BQ_ADAMW_NT=0 selects plain accesses)
@@ -80,7 +88,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamWTensor *__restric
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float q = pp[j] * decay;
-        const float gj = fminf(fmaxf(gg[j], -clip), clip);  // clip_grad_value_ (lib/solver.py:407-409); clip = inf: off
+        const float gj = clamp_keep_nan(gg[j], clip);  // clip_grad_value_ (lib/solver.py:407-409); clip = inf: off
         mm[j] = beta1 * mm[j] + omb1 * gj;
         vv[j] = beta2 * vv[j] + omb2 * gj * gj;
         const float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
@@ -97,7 +105,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamWTensor *__restric
     }
   } else {
     for (long i = off + threadIdx.x; i < end; i += 256) {
-      const float g = fminf(fmaxf(T.g[i], -clip), clip);
+      const float g = clamp_keep_nan(T.g[i], clip);
       const float q = T.p[i] * decay;
       const float m = beta1 * T.m[i] + omb1 * g;
       const float v = beta2 * T.v[i] + omb2 * g * g;

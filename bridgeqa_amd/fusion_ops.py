@@ -1575,14 +1575,17 @@ class _LMHeadCE(torch.autograd.Function):
         g = dloss.reshape(-1).to(torch.float32).contiguous()
         dl = _ext.lmhead_ce_dlogits(logits, lse, tgt.view(-1), g, V, eps)   # in place: the logits are consumed
         R = B * L
-        # dH (R, D) = dlogits (R, Vp) W (V, D): a 30 528-long contraction for a small output -> cut into pieces that
-        # accumulate with fp32 atomics (the rows of W beyond V are out of bounds for the DMA: zeros); in the deterministic
-        # mode each piece stores its own slab and the slabs are summed in piece order (_ext.gemm_grouped)
+        # dH (R, D) = dlogits (R, Vp) W (V, D): a 30 528-long contraction for a small output -> cut into pieces (the rows
+        # of W beyond V are out of bounds for the DMA: zeros); each piece stores its own slab and the slabs are summed in
+        # piece order (_ext.gemm_grouped, fixed_order) IN EVERY MODE: dH is the one cut contraction whose result every
+        # other gradient of the step descends from.  Accumulated with fp32 atomics, the arrival order of the pieces moved
+        # the bf16 rounding of an element of dH now and then, and the bf16 backward behind it carried that into every
+        # gradient upstream (1e-3 .. 1e-2 rel-L2 between two executions of one step from the same state, eager or replayed)
         dh = torch.zeros(R, D, dtype=torch.float32, device=h2.device)
         tiles = ((D + 63) // 64) * ((R + 31) // 32)
         ksplit = max(1, min(Vp // 64, (768 + tiles - 1) // tiles))
         _ext.gemm_grouped([dict(P=wb, Q=dl, out=dh, Kc=Vp, p_bytes=wb.shape[0] * wb.stride(0) * 2, ksplit=ksplit)],
-                          _ext.GEMM_P_XC | _ext.GEMM_OUT_F32, _ext.EPI_NONE, 32)
+                          _ext.GEMM_P_XC | _ext.GEMM_OUT_F32, _ext.EPI_NONE, 32, fixed_order=True)
         dhidden = dh.view(B, L, D).to(h_dtype)
         # dW (Vp, D) = dlogits^T h (fp32; its first V rows are the gradient of the tied embedding matrix)
         dw = torch.empty(Vp, D, dtype=torch.float32, device=h2.device)

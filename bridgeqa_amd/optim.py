@@ -11,7 +11,12 @@ class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_clip_value=None):
         """grad_clip_value: clamp every gradient element to [-v, v] inside the update kernel -- the reference's
         clip_grad_value_(parameters, 1.0) before optimizer.step() (lib/solver.py:407-409) at no extra pass; the stored
-        .grad tensors are left unclamped."""
+        .grad tensors are left unclamped.
+
+        Non-finite gradients behave as under clip_grad_value_ + torch.optim.AdamW: the in-kernel clamp keeps NaN (as
+        clamp_ does) and turns +-inf into +-grad_clip_value, so a NaN gradient element makes its parameter, both
+        moments and its bf16 shadow NaN -- the run dies visibly instead of training on a gradient of -grad_clip_value;
+        without clipping +-inf and NaN pass into the moments as they do in torch."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_clip_value = grad_clip_value
         betas_set = {tuple(g["betas"]) for g in self.param_groups}

@@ -164,6 +164,50 @@ def test_lm_head_dh_split_k(dev):
                                     ksplit=ksplit)], _ext.GEMM_P_XC | _ext.GEMM_OUT_F32, _ext.EPI_NONE, 32)
 
 
+def test_lm_head_backward_sums_dh_in_piece_order_in_the_default_mode(dev, monkeypatch):
+    """fusion_ops._LMHeadCE.backward with the mode OFF, at the c3 shape: dH is the first gradient of a step's backward and every
+    other gradient descends from it, so its cut contraction takes the fixed-order form in every mode.  The dH launch carries
+    GEMM_DET and more than one piece, writes a slab (not the fp32 atomics' target) and is the only launch of the backward that
+    does; dH repeats bit for bit over 12 backwards under load (dW, summed with fp32 atomics in this mode, is not asked to);
+    and the same backward runs, with the same dH, while the stream-K forms of the large-tile kernels are switched on."""
+    from bridgeqa_amd import _ext
+    from bridgeqa_amd import fusion_ops as ops
+    g = torch.Generator().manual_seed(30)
+    h = _rand((B3, A3, H), dev, 31).requires_grad_(True)
+    w = torch.nn.Parameter((torch.randn(V, H, generator=g) * 0.05).to(dev))
+    b = torch.nn.Parameter((torch.randn(V, generator=g) * 0.5).to(dev))
+    labels = torch.randint(0, V, (B3, A3), generator=g).to(dev)
+    gw = (torch.rand(B3, A3, generator=g) + 0.5).to(dev)
+    launches = []
+    real = _ext._gemm_grouped_launch
+
+    def spy(problems, flags, epilogue, tile):
+        launches.append((bool(flags & _ext.GEMM_DET), [int(p.get("ksplit", 1)) for p in problems], [tuple(p["out"].shape) for p in problems]))
+        return real(problems, flags, epilogue, tile)
+
+    def run():
+        h.grad, w.grad, b.grad = None, None, None
+        logits, loss = ops._LMHeadCE.apply(h, w, b, labels, 0.1)
+        (loss * gw).sum().backward()
+        return (h.grad.clone(),)
+    with _Mode(False):
+        monkeypatch.setattr(_ext, "_gemm_grouped_launch", spy)
+        first = run()[0]
+        monkeypatch.undo()
+        det = [l for l in launches if l[0]]
+        assert len(det) == 1 and det[0][1][0] > 1 and det[0][2] == [(B3 * A3, H)], launches
+        assert any(not l[0] and l[2] == [(VP, H)] for l in launches), launches       # dW: the default form
+        _repeat_under_load(dev, [run])
+        try:
+            _ext.streamk_enable(True)
+            _ext.streamk256_enable(True)
+            assert torch.equal(run()[0], first)
+        finally:
+            _ext.streamk_enable(False)
+            _ext.streamk256_enable(False)
+    assert torch.equal(run()[0], first)
+
+
 def test_weight_gradient_with_bias_column_sums(dev):
     """dW (N, K) of a text linear from two row sources (the second with accum, fusion_ops' twin K/V weight gradient) with the
     bias gradient from the same launches, and a bf16 input gradient with an epilogue column sum (taken by the fixed-order
