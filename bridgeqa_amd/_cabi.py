@@ -101,7 +101,7 @@ PROTOS, STRUCTS, DEFINES = parse(_read_headers())
 
 # Entry points added to ABI 6 after tests/test_cabi_cpu.py counted the two headers above by hand: they live in headers of their
 # own (bqhip_fusion.h includes them) and in a table of their own, derived by the same parser.  bind(lib, ADDITIVE_PROTOS).
-ADDITIVE_HEADERS = ("bqhip_lstm.h", "bqhip_scene.h")
+ADDITIVE_HEADERS = ("bqhip_lstm.h", "bqhip_scene.h", "bqhip_view.h")
 ADDITIVE_PROTOS, _, ADDITIVE_DEFINES = parse(_read_headers(ADDITIVE_HEADERS))
 
 

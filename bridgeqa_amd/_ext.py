@@ -650,6 +650,52 @@ def scene_prep(store, scene, object_id, choices, xf, out, table, augment=True, c
     return out
 
 
+# ---- image views: Pillow-exact bicubic resize and normalise (csrc/view_prep.hip, include/bqhip_view.h) ----------------------------
+VIEW_COLS = _cabi.ADDITIVE_DEFINES["BQ_VIEW_COLS"]             # long longs per view: first byte, H, W, horizontal / vertical table
+VIEW_DESC = _cabi.ADDITIVE_DEFINES["BQ_VIEW_DESC"]             # int32s per table: bounds offset, coefficient offset, ksize, extent
+VIEW_LDS_BYTES = _cabi.ADDITIVE_DEFINES["BQ_VIEW_LDS_BYTES"]   # LDS of a workgroup: 4096 for the table + 3 OW bytes per input row
+VIEW_CALLS = [0]           # launches of view_prep so far
+
+
+def _view_operand(t, shape, dtype, name):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError("view_prep: %s: CPU not supported (a device tensor is needed)" % name)
+    if t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError("view_prep: %s must be a %s tensor of shape %s, got %s %s"
+                           % (name, str(dtype).replace("torch.", ""), shape and tuple(shape), t.dtype, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise RuntimeError("view_prep: %s must be a contiguous tensor" % name)
+
+
+def view_prep(pixels, views, tab, desc, index, norm, out, OH, OW, tile_rows, lds_rows, patch=0):
+    """one batch of image views in one launch.  pixels (bytes) u8; views (NV, VIEW_COLS) i64; tab (n) i32 and desc (NT, VIEW_DESC)
+    i32: the coefficient tables; index (B) i64; norm (3, 256) f32 or bf16, which decides the output type; out: (B, 3, OH, OW), or
+    (B, OH OW / patch^2, 3 patch^2) with patch > 0, of norm's dtype.  Nothing is allocated and the host does not wait."""
+    if not torch.is_tensor(norm) or norm.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("view_prep: norm must be a float32 or bfloat16 tensor")
+    if not torch.is_tensor(index) or index.dim() != 1:
+        raise RuntimeError("view_prep: index must be (B,)")
+    OH, OW, patch, B = int(OH), int(OW), int(patch), index.shape[0]
+    if patch < 0 or (patch and (OH % patch or OW % patch)):
+        raise RuntimeError("view_prep: patch = %d does not divide the output %d x %d" % (patch, OH, OW))
+    oshape = (B, (OH // patch) * (OW // patch), 3 * patch * patch) if patch else (B, 3, OH, OW)
+    for t, shape, dtype, name in ((pixels, None, torch.uint8, "pixels"), (views, None, torch.int64, "views"),
+                                  (tab, None, torch.int32, "tab"), (desc, None, torch.int32, "desc"),
+                                  (index, (B,), torch.int64, "index"), (norm, (3, 256), norm.dtype, "norm"),
+                                  (out, oshape, norm.dtype, "out")):
+        _view_operand(t, shape, dtype, name)
+    if views.dim() != 2 or views.shape[1] != VIEW_COLS or desc.dim() != 2 or desc.shape[1] != VIEW_DESC or tab.dim() != 1 \
+            or pixels.dim() != 1:
+        raise RuntimeError("view_prep: pixels (n,), views (NV, %d), tab (n,) and desc (NT, %d) are needed" % (VIEW_COLS, VIEW_DESC))
+    _same_device(pixels, views, tab, desc, index, norm, out)
+    with torch.cuda.device(pixels.device):
+        VIEW_CALLS[0] += 1
+        _check(_lib.bq_view_prep(_p(pixels), pixels.shape[0], _p(views), views.shape[0], _p(tab), _p(desc), desc.shape[0],
+                                 tab.shape[0], _p(index), B, _p(norm), _p(out), OH, OW, int(tile_rows), int(lds_rows),
+                                 int(norm.dtype == torch.bfloat16), patch, _stream()), "view_prep")
+    return out
+
+
 # ---- attention of answer ranking: candidate sequences sharing their question's K / V (csrc/attn_rank.hip) -------------------------
 RANK_LMAX = _D["BQ_RANK_LMAX"]       # tokens per sequence attn_rank_self holds in registers
 RANK_QBLOCK = _D["BQ_RANK_QBLOCK"]   # queries a wave of attn_rank_cross carries through one loaded K / V chunk

@@ -68,11 +68,20 @@ def blip_itm(pretrained="", **kwargs):
 @torch.no_grad()
 def encode_views(model, images, batch_size=256):
     """images (N, 3, S, S) of one scene's views (any device) -> (N, embed_dim) normalised view features on the model's
-    device (eval_scene_best_views.py:199-214 + :246-249, without keeping the token sequences)"""
+    device (eval_scene_best_views.py:199-214 + :246-249, without keeping the token sequences).  Raw frames are accepted too:
+    uint8 (N, H, W, 3) of one size are uploaded as bytes and each chunk is preprocessed on the model's device at the model's
+    image size (view_data.preprocess_views: blip_utils.preprocess, bit for bit)."""
     dev = model.vision_proj.weight.device
+    raw = images.dtype == torch.uint8
+    if raw and (images.dim() != 4 or images.shape[3] != 3):
+        raise ValueError("encode_views: uint8 frames must be (N, H, W, 3), got %s" % (tuple(images.shape),))
     feats = []
     for i in range(0, images.shape[0], batch_size):
-        feats.append(model.image_features(model.visual_encoder(images[i:i + batch_size].to(dev, non_blocking=True))))
+        chunk = images[i:i + batch_size].to(dev, non_blocking=True)
+        if raw:
+            from .view_data import preprocess_views
+            chunk = preprocess_views(chunk, model.visual_encoder.patch_embed.img_size)
+        feats.append(model.image_features(model.visual_encoder(chunk)))
     return torch.cat(feats, 0)
 
 

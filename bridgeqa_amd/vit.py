@@ -31,6 +31,13 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
 
     def forward(self, x):
+        if x.dim() == 3:
+            # already unfolded, patch-major (B, patches, C * ph * pw) in the element order of the unfold below -- what
+            # view_data.ViewBatcher(layout="patches") writes; a bf16 input is also the GEMM's operand type as it is
+            K = self.proj.weight[0].numel()
+            assert x.shape[1] == self.num_patches and x.shape[2] == K, \
+                "Patch-major input %s doesn't match model (%d patches of %d)." % (tuple(x.shape), self.num_patches, K)
+            return ops.linear(x, self.proj.weight, self.proj.bias)
         B, C, H, W = x.shape
         assert H == self.img_size[0] and W == self.img_size[1], \
             "Input image size (%d*%d) doesn't match model (%d*%d)." % (H, W, self.img_size[0], self.img_size[1])
