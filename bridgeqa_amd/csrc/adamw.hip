@@ -120,16 +120,15 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamWTensor *__restric
 }  // namespace bq
 using namespace bq;
 
-extern "C" __attribute__((visibility("default"))) int bq_adamw_chunk_elems(void) { return ADAMW_CHUNK; }
-extern "C" __attribute__((visibility("default"))) int bq_adamw_tensor_bytes(void) { return (int)sizeof(AdamWTensor); }
+extern "C" int bq_adamw_chunk_elems(void) { return ADAMW_CHUNK; }
+extern "C" int bq_adamw_tensor_bytes(void) { return (int)sizeof(AdamWTensor); }
 
 // table: n_tensors records {p, g, m, v, shadow|NULL (pointers), n (int64), lr, wd (f32)} in DEVICE memory (layout =
 // struct AdamWTensor above, bq_adamw_tensor_bytes() each); chunks: n_chunks x {tensor index, chunk index} int32 pairs
 // in device memory covering every tensor in pieces of bq_adamw_chunk_elems() elements; step: device f32, the 1-based
 // step count t of THIS update.
-extern "C" __attribute__((visibility("default"))) int bq_adamw_multi(const void *table, const void *chunks, int n_chunks,
-                                                                     const float *step, float beta1, float beta2,
-                                                                     float eps, float grad_clip_value, void *stream) {
+extern "C" int bq_adamw_multi(const void *table, const void *chunks, int n_chunks, const float *step, float beta1,
+                              float beta2, float eps, float grad_clip_value, void *stream) {
   BQ_REQUIRE(n_chunks >= 0, BQ_EINVAL, "adamw: bad chunk count");
   if (n_chunks == 0) return BQ_OK;
   BQ_REQUIRE(table && chunks && step, BQ_EINVAL, "adamw: null pointer");

@@ -7,7 +7,6 @@
 #include <math.h>
 
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 
@@ -207,7 +206,7 @@ __global__ __launch_bounds__(256) void ap_curve_kernel(const unsigned char *__re
 
 using namespace bq;
 
-extern "C" __attribute__((visibility("default"))) int bq_ap_match(
+extern "C" int bq_ap_match(
     const double *box_tab, const int *det_box, const double *gt_tab, const int *seg_det, const int *seg_gt,
     const double *thresholds, unsigned char *tp, double *ovmax, int *jmax, int Nb, int D, int G, int S, int T,
     int max_seg_gt, void *stream) {
@@ -226,7 +225,7 @@ extern "C" __attribute__((visibility("default"))) int bq_ap_match(
   return check_launch("ap_match");
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_ap_curve(
+extern "C" int bq_ap_curve(
     const unsigned char *tp, const int *cls_off, const double *npos, double *rec, double *prec, double *ap,
     double *last_recall, int D, int C, int T, void *stream) {
   BQ_REQUIRE(T >= 1 && T <= AP_MAX_T, BQ_ELIMIT, "ap_curve: T = %d outside 1..%d", T, AP_MAX_T);

@@ -606,20 +606,38 @@ using namespace bq;
 // 235.2, tools/ab_attn.py, one box), inside the c3 step it is behind (34.0-34.1 ms against 33.8, tools/ab_step_attn.sh):
 // its static item walk cannot give way to the detector stream's workgroups the way block-by-block dispatch does.
 static int g_attn_persist = 0;
-extern "C" __attribute__((visibility("default"))) int bq_attn_set_persistent(int mask) {
+extern "C" int bq_attn_set_persistent(int mask) {
   const int prev = g_attn_persist;
   g_attn_persist = mask;
   return prev;
 }
-static int attn_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount;
-  }
-  return n;
+
+// ---- the kernels' argument block, built in ONE place (AttnDims is filled by name: a field added to it shifts nothing) ----
+struct Strides {
+  long bs, rs, hs;   // element strides: batch, row (token), head
+};
+// one key/value segment; o: the strides of O (forward) / dO (backward)
+static AttnDims attn_dims(int B, int H, int Lq, int Lk, int Lkp, Strides q, Strides k, Strides o, const float *mask, float scale,
+                          float p_drop, unsigned seed, const unsigned *seed_ptr, int causal) {
+  const DropCode drop = drop_code(p_drop);
+  AttnDims dm{};
+  dm.B = B; dm.H = H; dm.Lq = Lq; dm.Lk = Lk; dm.Lkp = Lkp;
+  dm.q_bs = q.bs; dm.q_rs = q.rs; dm.q_hs = q.hs;
+  dm.k_bs = k.bs; dm.k_rs = k.rs; dm.k_hs = k.hs;
+  dm.o_bs = o.bs; dm.o_rs = o.rs; dm.o_hs = o.hs;
+  dm.mask = mask; dm.scale = scale;
+  dm.inv_keep = drop.inv_keep; dm.drop_thresh = drop.thresh;
+  dm.seed = seed; dm.seed_ptr = seed_ptr;
+  dm.causal = causal ? 1 : 0;
+  dm.nkt1 = (Lk + AT_KB - 1) / AT_KB;
+  return dm;
+}
+// the second key/value segment on top (dK2 / dV2: backward only)
+static void attn_dims_segment2(AttnDims &dm, int Lk2, Strides k2, const void *K2, const void *V2, void *dK2, void *dV2) {
+  dm.Lk2 = Lk2;
+  dm.k2_bs = k2.bs; dm.k2_rs = k2.rs; dm.k2_hs = k2.hs;
+  dm.K2 = (const __bf16 *)K2; dm.V2 = (const __bf16 *)V2;
+  dm.dK2 = (__bf16 *)dK2; dm.dV2 = (__bf16 *)dV2;
 }
 
 // Q: bf16 (B, Lq, H, 64) / K, V: (B, Lk, H, 64) given by element strides (batch, token, head), 64 contiguous
@@ -630,7 +648,7 @@ static int attn_cu_count() {
 // dropout on the attention probabilities (stateless hash, regenerated by the backward); the effective seed is
 // seed_ptr[0] * 2654435761 + seed when seed_ptr (a device counter the caller bumps once per step) is given.
 // causal != 0 (Lq == Lk): keys after the query are masked as well.
-extern "C" __attribute__((visibility("default"))) int bq_attn_fwd(
+extern "C" int bq_attn_fwd(
     const void *Q, const void *K, const void *V, void *O, float *LSE, const float *mask, int B, int H, int Lq, int Lk,
     int Lkp, long q_bs, long q_rs, long q_hs, long k_bs, long k_rs, long k_hs, long o_bs, long o_rs, long o_hs,
     float scale, float p_drop, unsigned seed, const unsigned *seed_ptr, int causal, void *stream) {
@@ -641,9 +659,8 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_fwd(
              "attn_fwd: rows must be 16-byte aligned");
   BQ_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, BQ_EINVAL, "attn_fwd: bad dropout probability");
   BQ_REQUIRE(q_rs > 0 && k_rs > 0 && q_rs < (1 << 23) && k_rs < (1 << 23), BQ_EINVAL, "attn_fwd: row stride out of range");
-  AttnDims dm{B, H, Lq, Lk, 0, Lkp, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, o_bs, o_rs, o_hs, mask, scale,
-              1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), seed, seed_ptr, causal ? 1 : 0};
-  dm.nkt1 = (Lk + AT_KB - 1) / AT_KB;  // single key/value segment
+  const AttnDims dm = attn_dims(B, H, Lq, Lk, Lkp, {q_bs, q_rs, q_hs}, {k_bs, k_rs, k_hs}, {o_bs, o_rs, o_hs}, mask, scale, p_drop,
+                                seed, seed_ptr, causal);
   if (Lq <= AT_QW && Lk > 2 * AT_KB && (o_rs % 8) == 0 && (o_hs % 8) == 0) {
     hipLaunchKernelGGL(attn_fwd_narrow_kernel, dim3(1, B * H), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)Q,
                        (const __bf16 *)K, (const __bf16 *)V, (__bf16 *)O, LSE, dm);
@@ -652,7 +669,7 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_fwd(
   const bool plain = !mask && !causal && dm.drop_thresh == 0;
   if (plain && (g_attn_persist & 1)) {
     // resident grid (attn_fwd_persist_kernel): 3 workgroups per CU, every one walks (head, query block) items
-    const int rag = Lq % AT_QB, nqb = Lq / AT_QB + (rag > 1 ? 1 : 0), slots = 3 * attn_cu_count();
+    const int rag = Lq % AT_QB, nqb = Lq / AT_QB + (rag > 1 ? 1 : 0), slots = 3 * device_cus();
     // (few rounds only: with many items per workgroup the dispatcher's dynamic order balances better than a static walk --
     // L = 4097: 2.33 ms resident against 2.19 ms block by block; four workgroups per CU, i.e. 1.5 items each: 90.8 us
     // against 86.5 at L = 1025)
@@ -675,7 +692,7 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_fwd(
 // Backward of bq_attn_fwd.  dQ shares Q's strides, dK/dV share K's (V must be strided like K), dO has its own.
 // LSE and O (contiguous (B,Lq,H,64)) from the forward; DELTA: f32 [B*H][Lq] scratch (rowsum(dO*O), produced by the dQ
 // kernel, consumed by the dK/dV kernel).  mask / p_drop / seed / causal exactly as given to the forward.
-extern "C" __attribute__((visibility("default"))) int bq_attn_bwd(
+extern "C" int bq_attn_bwd(
     const void *Q, const void *K, const void *V, const void *dO, const float *LSE, const void *O, float *DELTA,
     const float *mask, void *dQ, void *dK, void *dV, int B, int H, int Lq, int Lk, int Lkp, long q_bs, long q_rs,
     long q_hs, long k_bs, long k_rs, long k_hs, long g_bs, long g_rs, long g_hs, float scale, float p_drop, unsigned seed,
@@ -688,22 +705,18 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_bwd(
   BQ_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, BQ_EINVAL, "attn_bwd: bad dropout probability");
   BQ_REQUIRE(q_rs > 0 && k_rs > 0 && g_rs > 0 && q_rs < (1 << 23) && k_rs < (1 << 23) && g_rs < (1 << 23), BQ_EINVAL,
              "attn_bwd: row stride out of range");
-  BwdDims dm{B, H, Lq, Lk, 0, Lkp, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, g_bs, g_rs, g_hs, mask, scale,
-             1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), seed, seed_ptr, causal ? 1 : 0};
-  dm.nkt1 = (Lk + AT_KB - 1) / AT_KB;  // single key/value segment
+  const BwdDims dm = attn_dims(B, H, Lq, Lk, Lkp, {q_bs, q_rs, q_hs}, {k_bs, k_rs, k_hs}, {g_bs, g_rs, g_hs}, mask, scale, p_drop,
+                               seed, seed_ptr, causal);
   hipStream_t st = (hipStream_t)stream;
   constexpr int dq_w = BQ_ATTN_DQ_MINW, dkv_w = 2;   // waves / SIMD: measured (dK/dV at 2: 0.34 -> 0.25 ms, round 1)
   const bool plain = !mask && !causal && dm.drop_thresh == 0;
-#define BQ_DQ(W, P) hipLaunchKernelGGL((attn_bwd_dq_kernel<W, P>), dim3((Lq + AT_QB - 1) / AT_QB, B * H), dim3(256), 0, \
-                                       st, (const __bf16 *)Q, (const __bf16 *)K, (const __bf16 *)V, (const __bf16 *)dO, \
-                                       LSE, (const __bf16 *)O, DELTA, (__bf16 *)dQ, dm)
   if (!plain && Lq <= AT_QB && Lk <= AT_QB) {
     hipLaunchKernelGGL(attn_bwd_small_kernel, dim3(1, B * H, 2), dim3(256), 0, st, (const __bf16 *)Q, (const __bf16 *)K,
                        (const __bf16 *)V, (const __bf16 *)dO, LSE, (const __bf16 *)O, DELTA, (__bf16 *)dQ, (__bf16 *)dK,
                        (__bf16 *)dV, dm);
     return check_launch("attn_bwd_small");
   }
-  const int rag_q = Lq % AT_QB, nqb_p = Lq / AT_QB + (rag_q > 1 ? 1 : 0), slots3 = 3 * attn_cu_count();
+  const int rag_q = Lq % AT_QB, nqb_p = Lq / AT_QB + (rag_q > 1 ? 1 : 0), slots3 = 3 * device_cus();
   if (plain && (g_attn_persist & 2) && (B * H) % 8 == 0 && slots3 % 8 == 0 && (long)B * H * nqb_p >= slots3 &&
       (long)B * H * nqb_p <= 4L * slots3)
     attn_bwd_dq_persist_launch(Q, K, V, dO, LSE, O, DELTA, dQ, dm, nqb_p, rag_q == 1 ? 1 : 0, slots3, st);   // resident grid, 3 per CU
@@ -711,21 +724,24 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_bwd(
     hipLaunchKernelGGL(attn_bwd_dq_narrow_kernel, dim3(1, B * H), dim3(256), 0, st, (const __bf16 *)Q, (const __bf16 *)K,
                        (const __bf16 *)V, (const __bf16 *)dO, LSE, (const __bf16 *)O, DELTA, (__bf16 *)dQ, dm);
   else
-  {
-    if (plain) BQ_DQ(dq_w, true); else BQ_DQ(2, false);   // (the general instantiation would spill 15 registers at four per CU)
-  }
-#undef BQ_DQ
+    with_flag(plain, [&](auto PL) {
+      constexpr bool P = decltype(PL)::value;   // (the general instantiation would spill 15 registers at four per CU: it gets 2)
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<P ? dq_w : 2, P>), dim3((Lq + AT_QB - 1) / AT_QB, B * H), dim3(256), 0, st,
+                         (const __bf16 *)Q, (const __bf16 *)K, (const __bf16 *)V, (const __bf16 *)dO, LSE, (const __bf16 *)O,
+                         DELTA, (__bf16 *)dQ, dm);
+    });
   int rc = check_launch("attn_bwd_dq");
   if (rc) return rc;
-#define BQ_DKV(W, P) hipLaunchKernelGGL((attn_bwd_dkv_kernel<W, P>), dim3((Lk + AT_QB - 1) / AT_QB, B * H), dim3(256), 0, \
-                                        st, (const __bf16 *)Q, (const __bf16 *)K, (const __bf16 *)V, (const __bf16 *)dO,  \
-                                        LSE, DELTA, (__bf16 *)dK, (__bf16 *)dV, dm)
-  const int rag_k = Lk % AT_QB, nkb_p = Lk / AT_QB + (rag_k > 1 ? 1 : 0), slots2 = 2 * attn_cu_count();
+  const int rag_k = Lk % AT_QB, nkb_p = Lk / AT_QB + (rag_k > 1 ? 1 : 0), slots2 = 2 * device_cus();
   if (plain && (g_attn_persist & 4) && (B * H) % 8 == 0 && slots2 % 8 == 0 && Lq > AT_KB && (long)B * H * nkb_p >= slots2 &&
       (long)B * H * nkb_p <= 6L * slots2)
     attn_bwd_dkv_persist_launch(Q, K, V, dO, LSE, DELTA, dK, dV, dm, nkb_p, rag_k == 1 ? 1 : 0, slots2, st);   // resident grid, 2 per CU
-  else if (plain) BQ_DKV(dkv_w, true); else BQ_DKV(dkv_w, false);
-#undef BQ_DKV
+  else
+    with_flag(plain, [&](auto PL) {
+      hipLaunchKernelGGL((attn_bwd_dkv_kernel<dkv_w, decltype(PL)::value>), dim3((Lk + AT_QB - 1) / AT_QB, B * H), dim3(256), 0, st,
+                         (const __bf16 *)Q, (const __bf16 *)K, (const __bf16 *)V, (const __bf16 *)dO, LSE, DELTA, (__bf16 *)dK,
+                         (__bf16 *)dV, dm);
+    });
   return check_launch("attn_bwd_dkv");
 }
 
@@ -739,7 +755,7 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_bwd(
 // mask: optional f32 [B][Lkp], Lkp = 64 * (ceil(Lk / 64) + ceil(Lk2 / 64)): segment 1's keys at [0, Lk), segment
 // 2's at [64 * ceil(Lk / 64), ... + Lk2), already multiplied by log2(e), 0 in the padding.  Everything else as
 // bq_attn_fwd (the kernels are the narrow-query ones: the four waves split the 64-key tiles of both segments).
-extern "C" __attribute__((visibility("default"))) int bq_attn_fwd2(
+extern "C" int bq_attn_fwd2(
     const void *Q, const void *K, const void *V, const void *K2, const void *V2, void *O, float *LSE, const float *mask,
     int B, int H, int Lq, int Lk, int Lk2, int Lkp, long q_bs, long q_rs, long q_hs, long k_bs, long k_rs, long k_hs,
     long k2_bs, long k2_rs, long k2_hs, long o_bs, long o_rs, long o_hs, float scale, float p_drop, unsigned seed,
@@ -753,18 +769,16 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_fwd2(
                  (k_hs % 8) == 0 && (k2_hs % 8) == 0 && (o_hs % 8) == 0, BQ_EINVAL,
              "attn_fwd2: rows must be 16-byte aligned");
   BQ_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, BQ_EINVAL, "attn_fwd2: bad dropout probability");
-  AttnDims dm{B, H, Lq, Lk, 0, Lkp, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, o_bs, o_rs, o_hs, mask, scale,
-              1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), seed, seed_ptr, 0};
-  dm.Lk2 = Lk2; dm.nkt1 = nkt1;
-  dm.k2_bs = k2_bs; dm.k2_rs = k2_rs; dm.k2_hs = k2_hs;
-  dm.K2 = (const __bf16 *)K2; dm.V2 = (const __bf16 *)V2;
+  AttnDims dm = attn_dims(B, H, Lq, Lk, Lkp, {q_bs, q_rs, q_hs}, {k_bs, k_rs, k_hs}, {o_bs, o_rs, o_hs}, mask, scale, p_drop, seed,
+                          seed_ptr, 0);
+  attn_dims_segment2(dm, Lk2, {k2_bs, k2_rs, k2_hs}, K2, V2, nullptr, nullptr);
   hipLaunchKernelGGL(attn_fwd_narrow_kernel, dim3(1, B * H), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)Q,
                      (const __bf16 *)K, (const __bf16 *)V, (__bf16 *)O, LSE, dm);
   return check_launch("attn_fwd2");
 }
 
 // Backward of bq_attn_fwd2: dQ like Q; dK / dV strided like K (segment 1), dK2 / dV2 like K2 (segment 2).
-extern "C" __attribute__((visibility("default"))) int bq_attn_bwd2(
+extern "C" int bq_attn_bwd2(
     const void *Q, const void *K, const void *V, const void *K2, const void *V2, const void *dO, const float *LSE,
     const void *O, float *DELTA, const float *mask, void *dQ, void *dK, void *dV, void *dK2, void *dV2, int B, int H,
     int Lq, int Lk, int Lk2, int Lkp, long q_bs, long q_rs, long q_hs, long k_bs, long k_rs, long k_hs, long k2_bs,
@@ -781,12 +795,9 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_bwd2(
              "attn_bwd2: rows must be 16-byte aligned");
   BQ_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, BQ_EINVAL, "attn_bwd2: bad dropout probability");
   BQ_REQUIRE(q_rs < (1 << 23) && g_rs < (1 << 23), BQ_EINVAL, "attn_bwd2: row stride out of range");
-  BwdDims dm{B, H, Lq, Lk, 0, Lkp, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, g_bs, g_rs, g_hs, mask, scale,
-             1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), seed, seed_ptr, 0};
-  dm.Lk2 = Lk2; dm.nkt1 = nkt1;
-  dm.k2_bs = k2_bs; dm.k2_rs = k2_rs; dm.k2_hs = k2_hs;
-  dm.K2 = (const __bf16 *)K2; dm.V2 = (const __bf16 *)V2;
-  dm.dK2 = (__bf16 *)dK2; dm.dV2 = (__bf16 *)dV2;
+  BwdDims dm = attn_dims(B, H, Lq, Lk, Lkp, {q_bs, q_rs, q_hs}, {k_bs, k_rs, k_hs}, {g_bs, g_rs, g_hs}, mask, scale, p_drop, seed,
+                         seed_ptr, 0);
+  attn_dims_segment2(dm, Lk2, {k2_bs, k2_rs, k2_hs}, K2, V2, dK2, dV2);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(attn_bwd_dq_narrow_kernel, dim3(1, B * H), dim3(256), 0, st, (const __bf16 *)Q, (const __bf16 *)K,
                      (const __bf16 *)V, (const __bf16 *)dO, LSE, (const __bf16 *)O, DELTA, (__bf16 *)dQ, dm);
@@ -815,16 +826,14 @@ static int fill_pair(const bq_attn_side *sd, int B, int H, float scale, float p_
     a.dO[g] = (const __bf16 *)s.dO; a.O[g] = (const __bf16 *)s.O;
     a.LSE[g] = s.LSE; a.LSEw[g] = s.LSE; a.DELTA[g] = s.DELTA;
     a.out[g] = (__bf16 *)s.out; a.dK[g] = (__bf16 *)s.dK; a.dV[g] = (__bf16 *)s.dV;
-    AttnDims dm{B, H, s.Lq, s.Lk, 0, s.Lkp, s.q_bs, s.q_rs, s.q_hs, s.k_bs, s.k_rs, s.k_hs, s.o_bs, s.o_rs, s.o_hs, s.mask,
-                scale, 1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), s.seed, seed_ptr, 0};
-    dm.nkt1 = (s.Lk + AT_KB - 1) / AT_KB;
-    a.dm[g] = dm;
+    a.dm[g] = attn_dims(B, H, s.Lq, s.Lk, s.Lkp, {s.q_bs, s.q_rs, s.q_hs}, {s.k_bs, s.k_rs, s.k_hs}, {s.o_bs, s.o_rs, s.o_hs},
+                        s.mask, scale, p_drop, s.seed, seed_ptr, 0);
   }
   return 0;
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_attn_fwd_pair(const bq_attn_side *sides, int B, int H, float scale,
-                                                                     float p_drop, const unsigned *seed_ptr, void *stream) {
+extern "C" int bq_attn_fwd_pair(const bq_attn_side *sides, int B, int H, float scale, float p_drop, const unsigned *seed_ptr,
+                                void *stream) {
   BQ_REQUIRE(sides && B > 0 && H > 0, BQ_EINVAL, "attn_fwd_pair: bad arguments");
   BQ_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, BQ_EINVAL, "attn_fwd_pair: bad dropout probability");
   AttnPair a;
@@ -834,8 +843,8 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_fwd_pair(const bq_
   return check_launch("attn_fwd_pair");
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_attn_bwd_pair(const bq_attn_side *sides, int B, int H, float scale,
-                                                                     float p_drop, const unsigned *seed_ptr, void *stream) {
+extern "C" int bq_attn_bwd_pair(const bq_attn_side *sides, int B, int H, float scale, float p_drop, const unsigned *seed_ptr,
+                                void *stream) {
   BQ_REQUIRE(sides && B > 0 && H > 0, BQ_EINVAL, "attn_bwd_pair: bad arguments");
   BQ_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, BQ_EINVAL, "attn_bwd_pair: bad dropout probability");
   AttnPair a;
@@ -898,7 +907,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const __bf16 *__restric
   }
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_attn_probs(
+extern "C" int bq_attn_probs(
     const void *Q, const void *K, const float *LSE, const float *mask, float *P, int B, int H, int Lq, int Lk, int Lkp,
     long q_bs, long q_rs, long q_hs, long k_bs, long k_rs, long k_hs, float scale, float p_drop, unsigned seed,
     const unsigned *seed_ptr, int causal, void *stream) {
@@ -906,8 +915,8 @@ extern "C" __attribute__((visibility("default"))) int bq_attn_probs(
   BQ_REQUIRE(!mask || (Lkp >= Lk), BQ_EINVAL, "attn_probs: mask row shorter than Lk");
   BQ_REQUIRE((k_rs % 8) == 0 && (k_hs % 8) == 0, BQ_EINVAL, "attn_probs: K rows must be 16-byte aligned");
   BQ_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, BQ_EINVAL, "attn_probs: bad dropout probability");
-  AttnDims dm{B, H, Lq, Lk, 0, Lkp, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, 0, 0, 0, mask, scale,
-              1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), seed, seed_ptr, causal ? 1 : 0};
+  const AttnDims dm = attn_dims(B, H, Lq, Lk, Lkp, {q_bs, q_rs, q_hs}, {k_bs, k_rs, k_hs}, {0, 0, 0}, mask, scale, p_drop, seed,
+                                seed_ptr, causal);
   hipLaunchKernelGGL(attn_probs_kernel, dim3((Lk + 255) / 256, B * H), dim3(256), 0, (hipStream_t)stream,
                      (const __bf16 *)Q, (const __bf16 *)K, LSE, P, dm);
   return check_launch("attn_probs");

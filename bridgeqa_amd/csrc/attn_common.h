@@ -6,7 +6,6 @@
 #include <stdlib.h>
 
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

@@ -20,7 +20,6 @@
 // Keys beyond the count are never loaded (a cache holds garbage there), out-of-range ancestry rows / positions are clamped
 // into the cache: a wrong table gives a wrong answer, never an access outside the buffers.
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

@@ -22,7 +22,6 @@
 //         registers, uses each loaded K / V chunk for all of them and loops over query blocks.
 // Keys beyond the count are never loaded; their registers are zero and their probability is exactly 0.
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

@@ -354,7 +354,7 @@ static bool bn_extents_ok(long R, int C, int S, int pool) {
          (!pool || (S > 0 && R % S == 0 && (1024 % S == 0 || S > 4096)));
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_bn_chunks(long R, int S, int pool) {
+extern "C" int bq_bn_chunks(long R, int S, int pool) {
   if (R <= 0) return 0;
   if (pool && S > 0) {
     const long G = R / S, gpc = bn_chunk_rows(R) / S > 0 ? bn_chunk_rows(R) / S : 1;
@@ -366,12 +366,9 @@ extern "C" __attribute__((visibility("default"))) int bq_bn_chunks(long R, int S
 // Training-mode statistics of x bf16 (R, C): scale/shift/mean/rstd f32 (C) out; running_mean/var (f32 C) and
 // num_batches_tracked (int64 scalar) updated in place when non-NULL (nn.BatchNorm2d training semantics: biased variance
 // to normalise, unbiased into running_var, momentum as given).  partial: bq_bn_chunks(R,0,0) * 2C floats of scratch.
-extern "C" __attribute__((visibility("default"))) int bq_bn_stats(const void *x, long R, int C, const float *gamma,
-                                                                  const float *beta, float *running_mean,
-                                                                  float *running_var, long long *num_batches_tracked,
-                                                                  float eps, float momentum, float *partial,
-                                                                  float *scale, float *shift, float *mean, float *rstd,
-                                                                  void *stream) {
+extern "C" int bq_bn_stats(const void *x, long R, int C, const float *gamma, const float *beta, float *running_mean,
+                           float *running_var, long long *num_batches_tracked, float eps, float momentum, float *partial,
+                           float *scale, float *shift, float *mean, float *rstd, void *stream) {
   BQ_REQUIRE(bn_extents_ok(R, C, 1, 0), BQ_ELIMIT, "bn_stats: C=%d unsupported", C);
   BQ_REQUIRE(R > 0, BQ_EINVAL, "bn_stats: empty batch");
   BQ_REQUIRE(x && gamma && beta && partial && scale && shift && mean && rstd, BQ_EINVAL, "bn_stats: null pointer");
@@ -385,27 +382,23 @@ extern "C" __attribute__((visibility("default"))) int bq_bn_stats(const void *x,
 
 // y = relu?(x*scale + shift): y bf16 (R, C), or with pool != 0 y bf16 (R/S, C) = max over each run of S rows; arg (pooled
 // layers, may be null): u8 (R/S, C) = the row 0 .. S-1 of each group's first maximum (S <= 256).
-extern "C" __attribute__((visibility("default"))) int bq_bn_apply_arg(const void *x, const float *scale, const float *shift,
-                                                                      void *y, void *arg, long R, int C, int S, int relu,
-                                                                      int pool, void *stream) {
+extern "C" int bq_bn_apply_arg(const void *x, const float *scale, const float *shift, void *y, void *arg, long R, int C,
+                               int S, int relu, int pool, void *stream) {
   BQ_REQUIRE(bn_extents_ok(R, C, S, pool) && (C >> 3) <= 256, BQ_ELIMIT, "bn_apply: C=%d S=%d unsupported", C, S);
   BQ_REQUIRE(!arg || (pool && S <= 256), BQ_EINVAL, "bn_apply: arg is for pooled layers with S <= 256");
   if (R == 0) return BQ_OK;
   BQ_REQUIRE(x && scale && shift && y, BQ_EINVAL, "bn_apply: null pointer");
   const long rows = pool ? R / S : R, threads = rows * (C >> 3);
   const dim3 grid((unsigned)((threads + 255) / 256));
-  hipStream_t st = (hipStream_t)stream;
-#define BQ_BN_APPLY(RL, PL) hipLaunchKernelGGL((bn_apply_kernel<RL, PL>), grid, dim3(256), 0, st, (const __bf16 *)x, \
-                                               scale, shift, (__bf16 *)y, R, C, S, (unsigned char *)arg)
-  if (relu) { if (pool) BQ_BN_APPLY(true, true); else BQ_BN_APPLY(true, false); }
-  else      { if (pool) BQ_BN_APPLY(false, true); else BQ_BN_APPLY(false, false); }
-#undef BQ_BN_APPLY
+  with_flags(relu, pool, [&](auto RL, auto PL) {
+    hipLaunchKernelGGL((bn_apply_kernel<decltype(RL)::value, decltype(PL)::value>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const __bf16 *)x, scale, shift, (__bf16 *)y, R, C, S, (unsigned char *)arg);
+  });
   return check_launch("bn_apply");
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_bn_apply(const void *x, const float *scale, const float *shift,
-                                                                  void *y, long R, int C, int S, int relu, int pool,
-                                                                  void *stream) {
+extern "C" int bq_bn_apply(const void *x, const float *scale, const float *shift, void *y, long R, int C, int S, int relu,
+                           int pool, void *stream) {
   return bq_bn_apply_arg(x, scale, shift, y, nullptr, R, C, S, relu, pool, stream);
 }
 
@@ -415,51 +408,46 @@ extern "C" int bq_bn_fold(const float *partial, float *out, int chunks, int W, v
   return check_launch("bn_fold");
 }
 
+// backward pass 1 of both backward entry points: the partial sums of g and g * xhat, one row of 2C floats per chunk
+static void bn_bwd_reduce_launch(const void *dy, const void *x, const float *scale, const float *shift, const float *mean,
+                                 const float *rstd, float *partial, long R, int C, int S, int relu, int pool, int chunks,
+                                 hipStream_t st) {
+  with_flags(relu, pool, [&](auto RL, auto PL) {
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<decltype(RL)::value, decltype(PL)::value>), dim3(chunks), dim3(256), 0, st,
+                       (const __bf16 *)dy, (const __bf16 *)x, scale, shift, mean, rstd, partial, R, C, S);
+  });
+}
+
 // The reduction half of bq_bn_backward alone: dgb f32 (2, C) = dbeta | dgamma (csrc/detbwd.hip computes the gradient w.r.t. x
 // inside its fused pass).  Same arguments as bq_bn_backward without dx.
-extern "C" __attribute__((visibility("default"))) int bq_bn_backward_reduce(const void *dy, const void *x, const float *scale,
-                                                                            const float *shift, const float *mean,
-                                                                            const float *rstd, float *partial, float *dgb, long R,
-                                                                            int C, int S, int relu, int pool, void *stream) {
+extern "C" int bq_bn_backward_reduce(const void *dy, const void *x, const float *scale, const float *shift, const float *mean,
+                                     const float *rstd, float *partial, float *dgb, long R, int C, int S, int relu, int pool,
+                                     void *stream) {
   BQ_REQUIRE(bn_extents_ok(R, C, S, pool) && (C >> 3) <= 256, BQ_ELIMIT, "bn_backward_reduce: C=%d S=%d unsupported", C, S);
   BQ_REQUIRE(R > 0, BQ_EINVAL, "bn_backward_reduce: empty batch");
   BQ_REQUIRE(dy && x && scale && shift && mean && rstd && partial && dgb, BQ_EINVAL, "bn_backward_reduce: null pointer");
   const int chunks = bq_bn_chunks(R, S, pool);
-  hipStream_t st = (hipStream_t)stream;
-#define BQ_BN_RED(RL, PL) hipLaunchKernelGGL((bn_bwd_reduce_kernel<RL, PL>), dim3(chunks), dim3(256), 0, st,           \
-                                             (const __bf16 *)dy, (const __bf16 *)x, scale, shift, mean, rstd, partial, \
-                                             R, C, S)
-  if (relu) { if (pool) BQ_BN_RED(true, true); else BQ_BN_RED(true, false); }
-  else      { if (pool) BQ_BN_RED(false, true); else BQ_BN_RED(false, false); }
-#undef BQ_BN_RED
+  bn_bwd_reduce_launch(dy, x, scale, shift, mean, rstd, partial, R, C, S, relu, pool, chunks, (hipStream_t)stream);
   return bq_bn_fold(partial, dgb, chunks, 2 * C, stream);
 }
 
 // Backward of bq_bn_stats + bq_bn_apply w.r.t. x, gamma, beta.  dy bf16 (R, C) or (R/S, C) when pooled;
 // dgb f32 (2, C) = dbeta | dgamma (written); dx bf16 (R, C); partial: bq_bn_chunks(R,S,pool) * 2C floats.
-extern "C" __attribute__((visibility("default"))) int bq_bn_backward(const void *dy, const void *x, const float *scale,
-                                                                     const float *shift, const float *mean,
-                                                                     const float *rstd, float *partial, float *dgb,
-                                                                     void *dx, long R, int C, int S, int relu, int pool,
-                                                                     void *stream) {
+extern "C" int bq_bn_backward(const void *dy, const void *x, const float *scale, const float *shift, const float *mean,
+                              const float *rstd, float *partial, float *dgb, void *dx, long R, int C, int S, int relu,
+                              int pool, void *stream) {
   BQ_REQUIRE(bn_extents_ok(R, C, S, pool) && (C >> 3) <= 256, BQ_ELIMIT, "bn_backward: C=%d S=%d unsupported", C, S);
   BQ_REQUIRE(R > 0, BQ_EINVAL, "bn_backward: empty batch");
   BQ_REQUIRE(dy && x && scale && shift && mean && rstd && partial && dgb && dx, BQ_EINVAL, "bn_backward: null pointer");
   const int chunks = bq_bn_chunks(R, S, pool);
   hipStream_t st = (hipStream_t)stream;
-#define BQ_BN_RED(RL, PL) hipLaunchKernelGGL((bn_bwd_reduce_kernel<RL, PL>), dim3(chunks), dim3(256), 0, st,           \
-                                             (const __bf16 *)dy, (const __bf16 *)x, scale, shift, mean, rstd, partial, \
-                                             R, C, S)
-  if (relu) { if (pool) BQ_BN_RED(true, true); else BQ_BN_RED(true, false); }
-  else      { if (pool) BQ_BN_RED(false, true); else BQ_BN_RED(false, false); }
-#undef BQ_BN_RED
+  bn_bwd_reduce_launch(dy, x, scale, shift, mean, rstd, partial, R, C, S, relu, pool, chunks, st);
   hipLaunchKernelGGL(bn_fold_kernel, dim3((2 * C + FOLD_COLS - 1) / FOLD_COLS), dim3(256), 0, st, partial, dgb, chunks, 2 * C);
   const long rows = pool ? R / S : R, threads = rows * (C >> 3);
   const dim3 grid((unsigned)((threads + 255) / 256));
-#define BQ_BN_DX(RL, PL) hipLaunchKernelGGL((bn_bwd_dx_kernel<RL, PL>), grid, dim3(256), 0, st, (const __bf16 *)dy,   \
-                                            (const __bf16 *)x, scale, shift, mean, rstd, dgb, (__bf16 *)dx, R, C, S)
-  if (relu) { if (pool) BQ_BN_DX(true, true); else BQ_BN_DX(true, false); }
-  else      { if (pool) BQ_BN_DX(false, true); else BQ_BN_DX(false, false); }
-#undef BQ_BN_DX
+  with_flags(relu, pool, [&](auto RL, auto PL) {
+    hipLaunchKernelGGL((bn_bwd_dx_kernel<decltype(RL)::value, decltype(PL)::value>), grid, dim3(256), 0, st, (const __bf16 *)dy,
+                       (const __bf16 *)x, scale, shift, mean, rstd, dgb, (__bf16 *)dx, R, C, S);
+  });
   return check_launch("bn_backward");
 }

@@ -3,14 +3,42 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
-#include "bqhip.h"
+// Every declaration of the ABI (bqhip.h and the additive headers): an entry point is DEFINED as `extern "C" <ret> bq_name(...)`
+// with this in sight, so a definition that disagrees with its header is "conflicting types", not a silently shifted argument.
+#include "bqhip_fusion.h"
 
 namespace bq {
 
 void set_error(const char *fmt, ...);
 int check_launch(const char *what);
 int device_cus();   // compute units of the CURRENT device (cached per device ordinal, pn2_ops.hip)
+
+// a drop probability p in [0, 1) as the kernels take it: kept values are scaled by inv_keep, a hash below thresh = p * 2^32 drops
+struct DropCode {
+  float inv_keep;
+  unsigned thresh;
+};
+inline DropCode drop_code(float p) { return DropCode{1.0f / (1.0f - p), (unsigned)((double)p * 4294967296.0)}; }
+
+// ---- run-time flag -> template argument (host) ---------------------------------------------------------------------------
+// with_flags(relu, pool, [&](auto RL, auto PL) { hipLaunchKernelGGL((kernel<decltype(RL)::value, decltype(PL)::value>), ...); });
+template <class F>
+inline void with_flag(bool a, F &&f) {
+  if (a) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F>
+inline void with_flags(bool a, bool b, F &&f) {
+  with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { f(A, B); }); });
+}
+// with_int<1, 2, 3, 4>(v, f): f(std::integral_constant<int, V>) for the first listed V == v; the LAST one when none is
+template <int V, int... Rest, class F>
+inline void with_int(int v, F &&f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+  else if (v == V) f(std::integral_constant<int, V>{});
+  else with_int<Rest...>(v, f);
+}
 
 // library-internal entry points shared between translation units (not part of include/*.h)
 extern "C" int bq_bn_fold(const float *partial, float *out, int chunks, int W, void *stream);                       // bn.hip

@@ -20,7 +20,6 @@
 // (tests/test_detloss_bound_gpu.py; tests/test_detloss_gpu.py against loss_helper.py and tests/golden/det_loss.npz).
 // torch.min's first-index tie rule kept.
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

@@ -5,7 +5,6 @@
 #include <type_traits>
 
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

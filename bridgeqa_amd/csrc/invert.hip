@@ -13,7 +13,6 @@
 // in round 5); everything here is plain kernels on caller-provided scratch.)
 
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

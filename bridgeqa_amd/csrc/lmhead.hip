@@ -10,7 +10,6 @@
 //           eps / V); the weight / hidden / bias gradients are then three launches of the GEMM family
 //           (dW = dlogits^T h, dH = dlogits W with the 30 528-long contraction split over workgroups, db = column sums).
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

@@ -360,7 +360,7 @@ __global__ __launch_bounds__(256) void gelu_fwd_kernel(const __bf16 *__restrict_
 using namespace bq;
 
 // y = GELU(x) (exact), n bf16 elements, n % 8 == 0, 16-B aligned
-extern "C" __attribute__((visibility("default"))) int bq_gelu_fwd_bf16(const void *x, void *y, long n, void *stream) {
+extern "C" int bq_gelu_fwd_bf16(const void *x, void *y, long n, void *stream) {
   BQ_REQUIRE(n >= 0 && n % 8 == 0, BQ_EINVAL, "gelu: n must be a multiple of 8");
   if (n == 0) return BQ_OK;
   BQ_REQUIRE(x && y && (((uintptr_t)x | (uintptr_t)y) & 15) == 0, BQ_EINVAL, "gelu: null / unaligned pointer");
@@ -378,23 +378,22 @@ extern "C" __attribute__((visibility("default"))) int bq_gelu_fwd_bf16(const voi
 // leaves them zero) -- counters of launches that may run concurrently must not alias.  Larger M: two launches.
 #define BQ_COLSUM_ONE_LAUNCH_ROWS 2048
 #define BQ_COLSUM_TALL_ROWS 1024
-extern "C" __attribute__((visibility("default"))) int bq_colsum_chunks(int M) {
+extern "C" int bq_colsum_chunks(int M) {
   if (M <= BQ_COLSUM_TALL_ROWS) return 1;
   const int rpc = M <= BQ_COLSUM_ONE_LAUNCH_ROWS ? 32 : 128;
   return M <= rpc ? 1 : (M + rpc - 1) / rpc;
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_colsum_bf16(const void *g, float *out, int M, int N,
-                                                                     float *partial, unsigned *counter, void *stream) {
+extern "C" int bq_colsum_bf16(const void *g, float *out, int M, int N, float *partial, unsigned *counter, void *stream) {
   BQ_REQUIRE(M >= 0 && N > 0 && N % 4 == 0, BQ_EINVAL, "colsum: bad extents");
   BQ_REQUIRE((g || M == 0) && out, BQ_EINVAL, "colsum: null pointer");
   hipStream_t st = (hipStream_t)stream;
+  const int vec = N % 8 == 0 ? 8 : 4;   // columns per thread
   if (M <= BQ_COLSUM_TALL_ROWS) {
     const dim3 grid((N + 255) / 256);
-    if (N % 8 == 0)
-      hipLaunchKernelGGL(colsum_tall_kernel<8>, grid, dim3(1024), 0, st, (const __bf16 *)g, out, M, N);
-    else
-      hipLaunchKernelGGL(colsum_tall_kernel<4>, grid, dim3(1024), 0, st, (const __bf16 *)g, out, M, N);
+    with_int<8, 4>(vec, [&](auto V) {
+      hipLaunchKernelGGL(colsum_tall_kernel<decltype(V)::value>, grid, dim3(1024), 0, st, (const __bf16 *)g, out, M, N);
+    });
     return check_launch("colsum");
   }
   const int chunks = bq_colsum_chunks(M);
@@ -404,13 +403,26 @@ extern "C" __attribute__((visibility("default"))) int bq_colsum_bf16(const void 
   const int rpc = chunks == 1 ? (M > 0 ? M : 1) : (one_launch ? 32 : 128);
   const dim3 grid((N + 255) / 256, chunks);
   unsigned *cnt = one_launch ? counter : nullptr;
-  if (N % 8 == 0)
-    hipLaunchKernelGGL(colsum_kernel<8>, grid, dim3(256), 0, st, (const __bf16 *)g, out, partial, cnt, M, N, rpc);
-  else
-    hipLaunchKernelGGL(colsum_kernel<4>, grid, dim3(256), 0, st, (const __bf16 *)g, out, partial, cnt, M, N, rpc);
+  with_int<8, 4>(vec, [&](auto V) {
+    hipLaunchKernelGGL(colsum_kernel<decltype(V)::value>, grid, dim3(256), 0, st, (const __bf16 *)g, out, partial, cnt, M, N, rpc);
+  });
   if (chunks > 1 && !one_launch)
     hipLaunchKernelGGL(colsum_fold_kernel, dim3((N + 63) / 64), dim3(256), 0, st, partial, out, chunks, N);
   return check_launch("colsum");
+}
+
+// the kernels' argument block, forward and backward (the backward takes no beta2; x_is_sum is the backward's alone)
+static LnArgs ln_args(int M, int H, float eps, float p_drop, float p_path, int rows_per_sample, unsigned seed,
+                      const unsigned *seed_ptr, int groups, const float *gamma2, const float *beta2, int x_is_sum) {
+  const DropCode drop = drop_code(p_drop), path = drop_code(p_path);
+  LnArgs a{};
+  a.M = M; a.H = H; a.eps = eps;
+  a.inv_keep = drop.inv_keep; a.thresh = drop.thresh;
+  a.seed = seed; a.seed_ptr = seed_ptr;
+  a.path_thresh = path.thresh; a.path_inv_keep = path.inv_keep; a.rows_per_sample = rows_per_sample;
+  a.groups = groups; a.gamma2 = gamma2; a.beta2 = beta2;
+  a.x_is_sum = x_is_sum;
+  return a;
 }
 
 // y = LayerNorm(dropout(x) + residual): x, residual, y bf16 (M, H) row-major, gamma/beta f32 (H), mean/rstd f32 (M)
@@ -430,8 +442,7 @@ static int ln_fwd_launch(const void *x, const void *residual, const float *gamma
   }
   BQ_REQUIRE(x && gamma && beta && y && mean && rstd, BQ_EINVAL, "drop_add_ln: null pointer");
   BQ_REQUIRE(p_path == 0.0f || rows_per_sample > 0, BQ_EINVAL, "drop_add_ln: rows_per_sample");
-  LnArgs a{M, H, eps, 1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), seed, seed_ptr,
-           (unsigned)((double)p_path * 4294967296.0), 1.0f / (1.0f - p_path), rows_per_sample, groups, gamma2, beta2, 0};
+  const LnArgs a = ln_args(M, H, eps, p_drop, p_path, rows_per_sample, seed, seed_ptr, groups, gamma2, beta2, 0);
 #ifndef BQ_LN_FWD_CAP
 #define BQ_LN_FWD_CAP 1024
 #endif
@@ -439,14 +450,13 @@ static int ln_fwd_launch(const void *x, const void *residual, const float *gamma
   const int Mg = M / groups;
   const dim3 grid(((Mg + 3) / 4) < fwd_cap ? (Mg + 3) / 4 : fwd_cap, groups);
   hipStream_t st = (hipStream_t)stream;
-#define BQ_LN_FWD(N)                                                                                           \
-  hipLaunchKernelGGL(drop_add_ln_fwd_kernel<N>, grid, dim3(256), 0, st, (const __bf16 *)x, (const __bf16 *)residual, \
-                     gamma, beta, (__bf16 *)y, (__bf16 *)sum_out, mean, rstd, zero_out, a)
-  switch (H / 256) { case 1: BQ_LN_FWD(1); break; case 2: BQ_LN_FWD(2); break; case 3: BQ_LN_FWD(3); break; default: BQ_LN_FWD(4); }
-#undef BQ_LN_FWD
+  with_int<1, 2, 3, 4>(H / 256, [&](auto NCH) {
+    hipLaunchKernelGGL(drop_add_ln_fwd_kernel<decltype(NCH)::value>, grid, dim3(256), 0, st, (const __bf16 *)x,
+                       (const __bf16 *)residual, gamma, beta, (__bf16 *)y, (__bf16 *)sum_out, mean, rstd, zero_out, a);
+  });
   return check_launch("drop_add_ln_fwd");
 }
-extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_fwd(
+extern "C" int bq_drop_add_ln_fwd(
     const void *x, const void *residual, const float *gamma, const float *beta, void *y, void *sum_out, float *mean,
     float *rstd, float *zero_out, int M, int H, float eps, float p_drop, float p_path, int rows_per_sample,
     unsigned seed, const unsigned *seed_ptr, void *stream) {
@@ -455,7 +465,7 @@ extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_fwd(
 }
 // The same over TWO row groups with their own LayerNorm parameters: rows [0, M/2) use gamma / beta, rows [M/2, M) gamma2 /
 // beta2 (the 2D and the 3D text stream of the twin encoder stacked in one tensor); zero_out: f32 (2, 2, H).
-extern "C" __attribute__((visibility("default"))) int bq_twin_drop_add_ln_fwd(
+extern "C" int bq_twin_drop_add_ln_fwd(
     const void *x, const void *residual, const float *gamma, const float *beta, const float *gamma2, const float *beta2,
     void *y, float *mean, float *rstd, float *zero_out, int M, int H, float eps, float p_drop, unsigned seed,
     const unsigned *seed_ptr, void *stream) {
@@ -484,41 +494,31 @@ static int ln_bwd_launch(const void *x, const void *residual, const float *gamma
              "drop_add_ln_bwd: null pointer");
   BQ_REQUIRE(!x_is_sum || (p_drop == 0.0f && groups == 1), BQ_EINVAL, "drop_add_ln_bwd_sum: no dropout, one row group");
   BQ_REQUIRE(p_path == 0.0f || rows_per_sample > 0, BQ_EINVAL, "drop_add_ln_bwd: rows_per_sample");
-  LnArgs a{M, H, eps, 1.0f / (1.0f - p_drop), (unsigned)((double)p_drop * 4294967296.0), seed, seed_ptr,
-           (unsigned)((double)p_path * 4294967296.0), 1.0f / (1.0f - p_path), rows_per_sample, groups, gamma2, nullptr, x_is_sum};
+  const LnArgs a = ln_args(M, H, eps, p_drop, p_path, rows_per_sample, seed, seed_ptr, groups, gamma2, nullptr, x_is_sum);
   // (with the cross-row prefetch: 256 / 384 / 512 / 640 / 1024 / 2048 workgroups -> 33.1 / 32.2 / 35.2 / 40.6 / 41.6 / 60.6 us
   // at the ViT shape, tools/bench_ln.py: every workgroup ends with 2 H float atomics on the same 2 H addresses)
   const int blocks = ln_bwd_blocks(M, groups);
   hipStream_t st = (hipStream_t)stream;
-#define BQ_LN_BWD(K, N)                                                                                         \
-  hipLaunchKernelGGL(K<N>, dim3(blocks, groups), dim3(256), 0, st, (const __bf16 *)x,                            \
-                     (const __bf16 *)residual, gamma, (const __bf16 *)dy, (const __bf16 *)dsum, mean, rstd,      \
-                     (__bf16 *)dx, (__bf16 *)dresidual, slab ? slab : dgb, a)
+  // the two kernels (one slab row per workgroup / float atomics into dgb) share their parameter list
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(blocks, groups), dim3(256), 0, st, (const __bf16 *)x, (const __bf16 *)residual, gamma,
+                       (const __bf16 *)dy, (const __bf16 *)dsum, mean, rstd, (__bf16 *)dx, (__bf16 *)dresidual,
+                       slab ? slab : dgb, a);
+  };
   if (slab) {
-    switch (H / 256) {
-      case 1: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 1); break;
-      case 2: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 2); break;
-      case 3: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 3); break;
-      default: BQ_LN_BWD(drop_add_ln_bwd_kernel_det, 4);
-    }
+    with_int<1, 2, 3, 4>(H / 256, [&](auto NCH) { launch(drop_add_ln_bwd_kernel_det<decltype(NCH)::value>); });
     const int N = groups * 2 * H;
     hipLaunchKernelGGL(ln_dgb_fold_det_kernel, dim3((N + 63) / 64), dim3(256), 0, st, (const float *)slab, dgb, blocks, N);
     return check_launch("drop_add_ln_bwd_det");
   }
-  switch (H / 256) {
-    case 1: BQ_LN_BWD(drop_add_ln_bwd_kernel, 1); break;
-    case 2: BQ_LN_BWD(drop_add_ln_bwd_kernel, 2); break;
-    case 3: BQ_LN_BWD(drop_add_ln_bwd_kernel, 3); break;
-    default: BQ_LN_BWD(drop_add_ln_bwd_kernel, 4);
-  }
-#undef BQ_LN_BWD
+  with_int<1, 2, 3, 4>(H / 256, [&](auto NCH) { launch(drop_add_ln_bwd_kernel<decltype(NCH)::value>); });
   return check_launch("drop_add_ln_bwd");
 }
-extern "C" __attribute__((visibility("default"))) long bq_drop_add_ln_bwd_det_slab_floats(int M, int H, int groups) {
+extern "C" long bq_drop_add_ln_bwd_det_slab_floats(int M, int H, int groups) {
   if (M <= 0 || H <= 0 || groups < 1) return 0;
   return (long)ln_bwd_blocks(M, groups) * groups * 2 * H;
 }
-extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd_det(
+extern "C" int bq_drop_add_ln_bwd_det(
     const void *x, const void *residual, const float *gamma, const float *gamma2, int groups, const void *dy, const void *dsum,
     const float *mean, const float *rstd, void *dx, void *dresidual, float *dgb, float *slab, int M, int H, float eps,
     float p_drop, float p_path, int rows_per_sample, unsigned seed, const unsigned *seed_ptr, int x_is_sum, void *stream) {
@@ -527,7 +527,7 @@ extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd_det(
   return ln_bwd_launch(x, residual, gamma, groups == 2 ? gamma2 : nullptr, groups, dy, dsum, mean, rstd, dx, dresidual, dgb, M, H,
                        eps, p_drop, p_path, rows_per_sample, seed, seed_ptr, stream, x_is_sum ? 1 : 0, slab);
 }
-extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd(
+extern "C" int bq_drop_add_ln_bwd(
     const void *x, const void *residual, const float *gamma, const void *dy, const void *dsum, const float *mean,
     const float *rstd, void *dx, void *dresidual, float *dgb, int M, int H, float eps, float p_drop, float p_path,
     int rows_per_sample, unsigned seed, const unsigned *seed_ptr, void *stream) {
@@ -539,7 +539,7 @@ extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd(
 // site drops from 150 to 125 MB, to 100 MB without stochastic depth); dx = dz * path scale, dresidual = dz (NULL with
 // p_path == 0: the two are the same tensor then and the caller hands dx to both).  The normalised value is re-formed from the
 // bf16-rounded sum where bq_drop_add_ln_bwd re-forms it from x and residual in fp32 (one bf16 rounding of the row apart).
-extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd_sum(
+extern "C" int bq_drop_add_ln_bwd_sum(
     const void *sum, const float *gamma, const void *dy, const void *dsum, const float *mean, const float *rstd, void *dx,
     void *dresidual, float *dgb, int M, int H, float eps, float p_path, int rows_per_sample, unsigned seed,
     const unsigned *seed_ptr, void *stream) {
@@ -547,7 +547,7 @@ extern "C" __attribute__((visibility("default"))) int bq_drop_add_ln_bwd_sum(
                        rows_per_sample, seed, seed_ptr, stream, 1);
 }
 // backward of bq_twin_drop_add_ln_fwd: dgb f32 (2, 2, H) = per row group dgamma then dbeta, accumulated
-extern "C" __attribute__((visibility("default"))) int bq_twin_drop_add_ln_bwd(
+extern "C" int bq_twin_drop_add_ln_bwd(
     const void *x, const void *residual, const float *gamma, const float *gamma2, const void *dy, const float *mean,
     const float *rstd, void *dx, void *dresidual, float *dgb, int M, int H, float eps, float p_drop, unsigned seed,
     const unsigned *seed_ptr, void *stream) {

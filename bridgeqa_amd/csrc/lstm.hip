@@ -27,7 +27,6 @@
 #include <math.h>
 
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

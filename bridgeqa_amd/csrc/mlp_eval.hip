@@ -13,7 +13,6 @@
 // block), so a lane's four accumulators are four CONSECUTIVE channels of one row: one 8-byte LDS store per row block.
 // Wave w computes output-channel tiles w, w + 4, ... for all 64 rows (16 tiles per pass).
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 namespace {
@@ -275,7 +274,7 @@ int me_check_layer(const bq_mlp_eval_layer &L, int k32, bool tail, int l) {
 
 using namespace bq;
 
-extern "C" __attribute__((visibility("default"))) int bq_mlp_eval(const bq_mlp_eval_desc *d, void *stream) {
+extern "C" int bq_mlp_eval(const bq_mlp_eval_desc *d, void *stream) {
   BQ_REQUIRE(d, BQ_EINVAL, "mlp_eval: null descriptor");
   BQ_REQUIRE(d->n_layers >= 1 && d->n_layers <= 3, BQ_EINVAL, "mlp_eval: %d layers (1..3)", d->n_layers);
   BQ_REQUIRE(d->R >= 0, BQ_EINVAL, "mlp_eval: bad extents");

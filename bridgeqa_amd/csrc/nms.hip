@@ -4,7 +4,6 @@
 // hull (remove_empty_box) and runs a numpy greedy NMS per scene.  Here: one kernel counts the points inside every box,
 // one kernel per launch does the greedy NMS of all scenes (one workgroup per scene), both on device tensors.
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(256) void nms_kernel(const float *__restrict__ box,
 
 using namespace bq;
 
-extern "C" __attribute__((visibility("default"))) int bq_box_point_count(
+extern "C" int bq_box_point_count(
     const float *points, const float *center, const float *size, const float *heading, int *count, int B, int N, int ld,
     int K, int cap, void *stream) {
   BQ_REQUIRE(points && center && size && heading && count, BQ_EINVAL, "box_point_count: null pointer");
@@ -125,7 +124,7 @@ extern "C" __attribute__((visibility("default"))) int bq_box_point_count(
   return check_launch("box_point_count");
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_nms_f64(
+extern "C" int bq_nms_f64(
     const float *box, const float *score, const int *cls, const unsigned char *valid, unsigned char *keep, int B, int K,
     double thresh, int old_type, int same_cls, void *stream) {
   BQ_REQUIRE(box && score && keep, BQ_EINVAL, "nms: null pointer");
@@ -136,7 +135,7 @@ extern "C" __attribute__((visibility("default"))) int bq_nms_f64(
   return check_launch("nms");
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_nms(
+extern "C" int bq_nms(
     const float *box, const float *score, const int *cls, const unsigned char *valid, unsigned char *keep, int B, int K,
     float thresh, int old_type, int same_cls, void *stream) {
   return bq_nms_f64(box, score, cls, valid, keep, B, K, (double)thresh, old_type, same_cls, stream);

@@ -619,7 +619,7 @@ extern "C" int bq_group_concat(const float *xyz, const float *new_xyz, const flo
 }
 
 // same, writing bf16 (the grouped tensor is the largest activation of the detector: 1.1 GB in fp32 at SA1)
-extern "C" __attribute__((visibility("default"))) int bq_group_concat_bf16(
+extern "C" int bq_group_concat_bf16(
     const float *xyz, const float *new_xyz, const float *features, const int32_t *idx, void *out, int B, int C, int N,
     int M, int S, float radius, int normalize, void *stream) {
   return group_concat_impl(xyz, new_xyz, features, idx, out, 1, B, C, N, M, S, radius, normalize, stream);
@@ -653,7 +653,7 @@ extern "C" int bq_group_concat_grad(const float *grad_out, const int32_t *idx, f
                                 normalize, stream);
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_group_concat_grad_bf16(
+extern "C" int bq_group_concat_grad_bf16(
     const void *grad_out, const int32_t *idx, float *grad_features, float *grad_xyz, float *grad_new_xyz, int B, int C,
     int N, int M, int S, float radius, int normalize, void *stream) {
   return group_concat_grad_impl(grad_out, 1, idx, grad_features, grad_xyz, grad_new_xyz, B, C, N, M, S, radius,
@@ -721,6 +721,8 @@ __global__ void debug_clock_kernel(float *out, int iters) {
   }
 }
 
+// THE ONE EXCEPTION to the entry-point rule: exported for tools/clock.py and declared in no header, so it is
+// the only definition that carries its visibility itself.
 extern "C" __attribute__((visibility("default"))) int bq_debug_clock_mhz(float *out, int blocks, int iters,
                                                                          void *stream) {
   hipLaunchKernelGGL(debug_clock_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, out, iters);
@@ -731,7 +733,7 @@ extern "C" __attribute__((visibility("default"))) int bq_debug_clock_mhz(float *
 // Point-major grouping (see group_concat_pm_kernel).  feats: f32 rows of C contiguous elements, batch stride f_bs
 // and row stride f_rs in elements (so a (B,N,3+C) interleaved cloud can be read in place); out: (B,M,S,3+C) f32 or
 // bf16.
-extern "C" __attribute__((visibility("default"))) int bq_group_concat_pm(
+extern "C" int bq_group_concat_pm(
     const float *xyz, const float *new_xyz, const float *feats, long f_bs, long f_rs, const int32_t *idx, void *out,
     int out_bf16, int B, int C, int N, int M, int S, float radius, int normalize, int ld, void *stream) {
   BQ_REQUIRE(B >= 0 && C >= 0 && N >= 0 && M >= 0 && S >= 0, BQ_EINVAL, "group_concat_pm: bad extents");
@@ -757,7 +759,7 @@ extern "C" __attribute__((visibility("default"))) int bq_group_concat_pm(
 
 // grad_out: (B,M,S,3+C) f32 or bf16; grad_feats (B,N,C) f32, grad_xyz (B,N,3), grad_new_xyz (B,M,3): zero_init, each
 // optional (NULL).
-extern "C" __attribute__((visibility("default"))) int bq_group_concat_pm_grad(
+extern "C" int bq_group_concat_pm_grad(
     const void *grad_out, int in_bf16, const int32_t *idx, float *grad_feats, float *grad_xyz, float *grad_new_xyz,
     int B, int C, int N, int M, int S, float radius, int normalize, int ld, void *stream) {
   BQ_REQUIRE(B >= 0 && C >= 0 && N >= 0 && M >= 0 && S >= 0, BQ_EINVAL, "group_concat_pm_grad: bad extents");

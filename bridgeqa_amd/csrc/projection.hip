@@ -5,7 +5,6 @@
 // features into the points one frame at a time.  Here: ONE launch maps every (frame, point) pair to its pixel (or -1) and
 // ONE launch walks the frames of every point, both streaming (HBM-bound integer / gather work, no LDS, no MFMA).
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(1024) void fuse_point_features_kernel(const int *__
 
 using namespace bq;
 
-extern "C" __attribute__((visibility("default"))) int bq_project_points(
+extern "C" int bq_project_points(
     const float *points, const float *depth, const float *frames, int *pix, int F, int N, int W, int H, float fx, float fy,
     float cx, float cy, float depth_min, float depth_max, float accuracy, void *stream) {
   BQ_REQUIRE(points && depth && frames && pix, BQ_EINVAL, "project_points: null pointer");
@@ -120,7 +119,7 @@ extern "C" __attribute__((visibility("default"))) int bq_project_points(
   return check_launch("project_points");
 }
 
-extern "C" __attribute__((visibility("default"))) int bq_fuse_point_features(
+extern "C" int bq_fuse_point_features(
     const int *pix, const float *feat, float *out, int F, int N, int HW, int C, int maxpool, void *stream) {
   BQ_REQUIRE(pix && feat && out, BQ_EINVAL, "fuse_point_features: null pointer");
   BQ_REQUIRE(F > 0 && N > 0 && HW > 0, BQ_EINVAL, "fuse_point_features: bad extents");

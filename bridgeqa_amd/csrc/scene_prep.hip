@@ -22,7 +22,6 @@
 // scene_vote_kernel    one thread per sampled point: its instance's entry, the first-position rule, 9 floats and the mask.
 // Integer min / max do not depend on the order of arrival: two runs give the same bits.  There is no float atomic.
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 

@@ -76,15 +76,14 @@ __global__ __launch_bounds__(256) void transpose_multi_bf16_kernel(const Transpo
 }  // namespace bq
 using namespace bq;
 
-extern "C" __attribute__((visibility("default"))) int bq_transpose_tensor_bytes(void) { return (int)sizeof(TransposeTensor); }
+extern "C" int bq_transpose_tensor_bytes(void) { return (int)sizeof(TransposeTensor); }
 
 // table: n_tensors records {src, dst (pointers), N, K, ld, tiles_k = K / 64 (int32)} in DEVICE memory (layout = struct
 // TransposeTensor, bq_transpose_tensor_bytes() each; N and K multiples of 64, ld a multiple of 8, 16-byte aligned
 // pointers: the CALLER guarantees it, the table is not read on the host); chunks: n_chunks x {tensor index, tile index}
 // int32 pairs covering every 64 x 64 tile (tile index = (n / 64) * tiles_k + k / 64).  max_wgs > 0: at most that many
 // workgroups, each walking several tiles (<= 0: one workgroup per tile).
-extern "C" __attribute__((visibility("default"))) int bq_transpose_multi_bf16(const void *table, const void *chunks, int n_chunks,
-                                                                              int max_wgs, void *stream) {
+extern "C" int bq_transpose_multi_bf16(const void *table, const void *chunks, int n_chunks, int max_wgs, void *stream) {
   BQ_REQUIRE(n_chunks >= 0, BQ_EINVAL, "transpose_multi: bad chunk count");
   if (n_chunks == 0) return BQ_OK;
   BQ_REQUIRE(table && chunks, BQ_EINVAL, "transpose_multi: null pointer");

@@ -18,7 +18,6 @@
 // Every index that comes from memory (view, table, window start and length, row count) is clamped or checked against the
 // extents before it is used: see the header.
 #include "bq_common.h"
-#include "bqhip_fusion.h"
 
 namespace bq {
 
@@ -156,26 +155,6 @@ __global__ __launch_bounds__(VP_THREADS) void view_prep_kernel(
   }
 }
 
-template <typename T>
-static void view_prep_launch(int vec4, int patch, dim3 grid, size_t lds, hipStream_t stream, const unsigned char *pixels,
-                             long n_pixels, const long long *views, int NV, const int32_t *tab, const int32_t *desc, int NT,
-                             long n_tab,
-                             const long long *index, const void *norm, void *out, int OH, int OW, int tile_rows, int lds_rows,
-                             int tiles) {
-#define BQ_VIEW_LAUNCH(VEC, PATCH)                                                                                         \
-  hipLaunchKernelGGL((view_prep_kernel<T, VEC, PATCH>), grid, dim3(VP_THREADS), lds, stream, pixels, n_pixels, views, NV, \
-                     tab, desc, NT, n_tab, index, (const T *)norm, (T *)out, OH, OW, tile_rows, lds_rows, tiles, patch)
-  if (vec4 && patch)
-    BQ_VIEW_LAUNCH(4, true);
-  else if (vec4)
-    BQ_VIEW_LAUNCH(4, false);
-  else if (patch)
-    BQ_VIEW_LAUNCH(1, true);
-  else
-    BQ_VIEW_LAUNCH(1, false);
-#undef BQ_VIEW_LAUNCH
-}
-
 }  // namespace bq
 
 extern "C" int bq_view_prep(const unsigned char *pixels, long n_pixels, const long long *views, int NV, const int32_t *tab,
@@ -200,11 +179,14 @@ extern "C" int bq_view_prep(const unsigned char *pixels, long n_pixels, const lo
   const size_t elem = out_bf16 ? 2 : 4;
   const int vec4 = OW % 4 == 0 && ((size_t)out % (4 * elem)) == 0 && (patch == 0 || patch % 4 == 0);
   const dim3 grid((unsigned)(tiles * B));
-  if (out_bf16)
-    view_prep_launch<unsigned short>(vec4, patch, grid, (size_t)lds, (hipStream_t)stream, pixels, n_pixels, views, NV, tab, desc,
-                                     NT, n_tab, index, norm, out, OH, OW, tile_rows, lds_rows, (int)tiles);
-  else
-    view_prep_launch<float>(vec4, patch, grid, (size_t)lds, (hipStream_t)stream, pixels, n_pixels, views, NV, tab, desc, NT, n_tab,
-                            index, norm, out, OH, OW, tile_rows, lds_rows, (int)tiles);
+  const auto launch = [&](auto elem) {   // elem: a value of the output's element type (bf16 travels as its 16 bits)
+    using T = decltype(elem);
+    with_flags(vec4, patch, [&](auto V4, auto PATCH) {
+      hipLaunchKernelGGL((view_prep_kernel<T, decltype(V4)::value ? 4 : 1, decltype(PATCH)::value>), grid, dim3(VP_THREADS),
+                         (size_t)lds, (hipStream_t)stream, pixels, n_pixels, views, NV, tab, desc, NT, n_tab, index,
+                         (const T *)norm, (T *)out, OH, OW, tile_rows, lds_rows, (int)tiles, patch);
+    });
+  };
+  if (out_bf16) launch((unsigned short)0); else launch(0.0f);
   return check_launch("view_prep");
 }

@@ -2,8 +2,10 @@
 The parser is held to truths it did not produce: a count of the headers' BQ_API declarations, struct layouts printed by the
 host C compiler, and signatures / values written out by hand.  No GPU, no compute."""
 import ctypes
+import glob
 import os
 import re
+import shutil
 import subprocess
 import sys
 import types
@@ -129,6 +131,117 @@ def test_missing_header_and_stale_library_are_named(tmp_path, monkeypatch):
     monkeypatch.setitem(_cabi.PROTOS, "bq_declared_not_exported", (_i, [_vp]))
     with pytest.raises(ImportError, match=r"bq_declared_not_exported.*stale library: python -m bridgeqa_amd.build --force"):
         _cabi.bind(ctypes.CDLL(_ext.library_path()))
+
+
+# ---- the other half: every definition is compiled against its declaration -------------------------------------------------
+# The rule: an entry point is defined as `extern "C" <ret> bq_name(...)`, no visibility attribute, in a source
+# that includes the header declaring it.  Then a definition that disagrees with the header does not compile.
+CSRC = os.path.join(ROOT, "bridgeqa_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+HAVE_HIPCC = os.path.exists(HIPCC)
+ALL_HEADERS = _cabi.HEADERS + _cabi.ADDITIVE_HEADERS
+UNDECLARED = {"bq_debug_clock_mhz"}       # exported for tools/clock.py, in no header: the one exception
+
+
+def _all_declared():
+    return set(_cabi.PROTOS) | set(_cabi.ADDITIVE_PROTOS)
+
+
+def _definitions():
+    """{bq_ name: [(source file, everything on its line in front of the name)]} of every function DEFINITION in csrc/*.hip"""
+    found = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+        text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        text = re.sub(r"//[^\n]*", "", text)
+        for m in re.finditer(r"^([^\n;{}]*?)\b(bq_\w+)\s*\(([^(){};]*)\)\s*\{", text, flags=re.M):
+            found.setdefault(m.group(2), []).append((os.path.basename(path), m.group(1)))
+    return found
+
+
+def test_exported_symbols_are_the_declared_ones():
+    from bridgeqa_amd import _ext
+    out = subprocess.check_output(["nm", "-D", "--defined-only", _ext.library_path()]).decode()
+    exported = {ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T" and ln.split()[2].startswith("bq_")}
+    assert len(_all_declared()) == 103
+    assert exported == _all_declared() | UNDECLARED
+
+
+def test_every_definition_is_extern_c_without_an_attribute():
+    defs = _definitions()
+    for name in sorted(_all_declared()):
+        assert len(defs.get(name, ())) == 1, (name, defs.get(name))
+        src, head = defs[name][0]
+        assert re.fullmatch(r'extern "C" (?:const )?\w+(?: \w+)* ?\**', head), (name, src, head)
+        assert "attribute" not in head and "visibility" not in head and "BQ_API" not in head, (name, src, head)
+    # the exception carries its visibility itself, and nothing else does
+    assert [h for s, h in defs["bq_debug_clock_mhz"]] == ['extern "C" __attribute__((visibility("default"))) int ']
+    others = "".join(re.sub(r"[^\n]*bq_debug_clock_mhz[^\n]*", "", open(p).read()) for p in glob.glob(os.path.join(CSRC, "*.hip")))
+    assert 'visibility("default")' not in others
+
+
+def _declaring_header(name):
+    hits = [h for h in ALL_HEADERS
+            if re.search(r"\bBQ_API\s[^;(]*?\b%s\s*\(" % name, re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S))]
+    assert len(hits) == 1, (name, hits)
+    return hits[0]
+
+
+def _first_mention(preprocessed, names):
+    """{name: basename of the file whose text holds the first `name(` of a host-only preprocessed source}, by its line markers"""
+    first, cur = {}, None
+    want = re.compile(r"\b(%s)\s*\(" % "|".join(sorted(names)))
+    for line in preprocessed.splitlines():
+        m = re.match(r'# \d+ "([^"]*)"', line)
+        if m:
+            cur = os.path.basename(m.group(1))
+            continue
+        for n in want.findall(line):
+            first.setdefault(n, cur)
+    return first
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="no hipcc")
+def test_every_definition_sees_its_declaration():
+    """the host-only preprocessed text of the defining source meets the name in the declaring header first, before the definition"""
+    from bridgeqa_amd import build
+    by_src = {}
+    for name, sites in _definitions().items():
+        if name in _all_declared():
+            by_src.setdefault(sites[0][0], set()).add(name)
+    assert sum(len(v) for v in by_src.values()) == 103
+    incl = [a for i, a in enumerate(build.FLAGS) if a == "-I" or (i and build.FLAGS[i - 1] == "-I")]
+    procs = {src: subprocess.Popen([HIPCC, "--offload-arch=gfx950", "-std=c++17", "--cuda-host-only", "-E"] + incl +
+                                   [os.path.join(CSRC, src)], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+             for src in by_src}
+    for src, p in procs.items():
+        out, err = p.communicate()
+        assert p.returncode == 0, (src, err.decode()[-2000:])
+        first = _first_mention(out.decode(), by_src[src])
+        for name in sorted(by_src[src]):
+            assert first.get(name) == _declaring_header(name), (name, src, first.get(name))
+
+
+def test_first_mention_tells_a_source_without_its_header():
+    """the check above fails for a source that stops including the header: its first mention is then the definition itself"""
+    with_hdr = '# 1 "x/bn.hip"\n# 1 "inc/bqhip_fusion.h" 1\nint bq_bn_chunks(long R);\n# 3 "x/bn.hip" 2\nextern "C" int bq_bn_chunks(long R) {\n'
+    without = '# 1 "x/bn.hip"\nextern "C" int bq_bn_chunks(long R) {\n'
+    assert _first_mention(with_hdr, {"bq_bn_chunks"}) == {"bq_bn_chunks": "bqhip_fusion.h"}
+    assert _first_mention(without, {"bq_bn_chunks"}) == {"bq_bn_chunks": "bn.hip"}
+    assert _declaring_header("bq_bn_chunks") == "bqhip_fusion.h" and _declaring_header("bq_view_prep") == "bqhip_view.h"
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="no hipcc")
+@pytest.mark.parametrize("first_param, conflict", [("int R", True), ("long R", False)])
+def test_a_definition_that_disagrees_with_its_header_does_not_compile(tmp_path, first_param, conflict):
+    """the mechanism itself: the header says `long R`"""
+    src = str(tmp_path / "entry.hip")
+    open(src, "w").write('#include "bqhip_fusion.h"\nextern "C" int bq_bn_chunks(%s, int S, int pool) { return 0; }\n' % first_param)
+    r = subprocess.run([HIPCC, "--cuda-host-only", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), src],
+                       capture_output=True, text=True)
+    if conflict:
+        assert r.returncode != 0 and "conflicting types" in r.stderr, r.stderr
+    else:
+        assert r.returncode == 0, r.stderr
 
 
 def test_cabi_needs_neither_torch_nor_the_library():
