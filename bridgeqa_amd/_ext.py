@@ -12,7 +12,8 @@ import os
 
 import torch  # must be imported first: libbqhip.so resolves libamdhip64.so.7 to torch's copy
 
-from . import _cabi
+from . import _cabi, gemm_route
+from .gemm_route import GEMM_TILE_ROWS, TILE256_MIN_K, pick_tile  # noqa: F401  (the GEMM tile policy; tools flip these by name)
 
 # (BQHIP_LIB: another build of the same sources, e.g. with a measurement macro set -- A/B runs in one gpurun call)
 _LIB_PATH = os.environ.get("BQHIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libbqhip.so")
@@ -1250,9 +1251,6 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_CE, EPI_ADD = (
     _D["BQ_GEMM_EPI_" + n] for n in ("NONE", "BIAS", "BIAS_GELU", "DGELU", "BIAS_CE", "ADD"))
 GEMM_DET = _D["BQ_GEMM_DET"]   # set by gemm_grouped itself in the deterministic mode
 _GemmDesc = _cabi.STRUCTS["bq_gemm_desc"]
-GEMM_TILE_ROWS = 1024  # problems with at least this many j rows (and i columns >= 256) run on the large-tile kernels
-# Large problems whose output is bf16 with a K-contiguous Q (forward, input gradient) take the 256 x 128 persistent kernel
-# (csrc/gemm_mid.hip: two workgroups per CU; round 3 A/B against the 256 x 256 one: 38.8 vs 39.2 ms per c3 step).
 
 
 def _mat(t, name):
@@ -1285,22 +1283,6 @@ def _mat_rows(t, name):
     return (B * R, C), ld, R, bs
 
 
-# forward / dX launches (K-contiguous operands, plain or bias epilogue) whose contraction is at least this long run on the
-# 256 x 256 kernel instead of the 256 x 128 one: since round 6's K loop (two 32-MFMA phases, no compiler fence) it is level or
-# ahead alone on fc2 forward (71 against 77 us), dX through fc1 (71 / 72) and dX through qkv (56 / 56), and inside the c3 step
-# 31.81 against 32.05 ms (five interleaved pairs, 7 of 8 pairs over two calls in favour; profiles/r06_tile256_long_k.txt).
-# 0 = never (tools/ab_bench.py "_ext.TILE256_MIN_K[0]=0")
-TILE256_MIN_K = [2304]
-
-
-def pick_tile(Ni, Nj, q_xc, mid_ok=False):
-    if Nj >= GEMM_TILE_ROWS and Ni >= 256:
-        return 128 if mid_ok else 256
-    if q_xc or Nj > 512:  # (64-row tiles from 100 / 200 rows up: measured 0.3-0.4 ms SLOWER per c3 step)
-        return 64
-    return 32
-
-
 def gemm_grouped(problems, flags, epilogue=EPI_NONE, tile=None, fixed_order=False):
     """One launch for a list of problems out[j][i] = epilogue(sum_kc P(i,kc) Q(j,kc)) (include/bqhip_fusion.h,
     bq_gemm_bf16).  problems: dicts with P, Q, out (2-D tensors, contiguous last dim) and optional bias (fp32 (Ni,)),
@@ -1312,71 +1294,59 @@ def gemm_grouped(problems, flags, epilogue=EPI_NONE, tile=None, fixed_order=Fals
     return _gemm_grouped_launch(problems, flags, epilogue, tile)
 
 
-def _gemm_grouped_launch(problems, flags, epilogue, tile):
+def _gemm_pack(d, pr, flags, epilogue):
+    """validate one problem dict and fill its bq_gemm_desc `d`; returns what the tile policy reads of it (gemm_route.Shape)"""
     pxc, qxc, f32 = bool(flags & GEMM_P_XC), bool(flags & GEMM_Q_XC), bool(flags & GEMM_OUT_F32)
+    P, Q, out = _mat(pr["P"], "P"), pr["Q"], pr["out"]
+    qshape, ldq, q_rpb, q_bs = _mat_rows(Q, "Q")
+    oshape, ldo, o_rpb, o_bs = _mat_rows(out, "out")
+    if P.dtype != torch.bfloat16 or Q.dtype != torch.bfloat16:
+        raise RuntimeError("gemm: operands must be bf16")
+    if out.dtype != (torch.float32 if f32 else torch.bfloat16):
+        raise RuntimeError("gemm: out must be %s" % ("float32" if f32 else "bfloat16"))
+    Ni, Kc = (P.shape[1], P.shape[0]) if pxc else (P.shape[0], P.shape[1])
+    Nj, Kq = (qshape[1], qshape[0]) if qxc else (qshape[0], qshape[1])
+    Ni = int(pr.get("Ni", Ni))  # output wider than P's rows (padded vocabulary): P's true extent goes in p_bytes
+    if (Kq != Kc and "Kc" not in pr) or tuple(oshape) != (Nj, Ni):
+        raise RuntimeError("gemm: shape mismatch P%s Q%s out%s" % (tuple(P.shape), tuple(Q.shape), tuple(out.shape)))
+    d.P, d.Q, d.out = P.data_ptr(), Q.data_ptr(), out.data_ptr()
+    bias, out2, aux, colsum = pr.get("bias"), pr.get("out2"), pr.get("aux"), pr.get("colsum")
+    if bias is not None and (bias.dtype not in (torch.float32, torch.bfloat16) or bias.numel() != Ni
+                             or not bias.is_contiguous()):
+        raise RuntimeError("gemm: bias must be a contiguous fp32 or bf16 (Ni,) tensor")
+    d.bias_bf16 = int(bias is not None and bias.dtype == torch.bfloat16)
+    # (weight-gradient form: colsum (Nj,) receives the column sums of Q over the contraction; with ksplit > 1 it is
+    # accumulated with atomics and must arrive zeroed)
+    n_cs = Nj if (pxc and qxc and f32) else Ni
+    if epilogue != EPI_BIAS_CE and colsum is not None and (colsum.dtype != torch.float32 or colsum.numel() != n_cs
+                                                           or not colsum.is_contiguous()):
+        raise RuntimeError("gemm: colsum must be a contiguous fp32 (%d,) tensor" % n_cs)
+    for t, nm in ((out2, "out2"), (aux, "aux")):
+        if epilogue != EPI_BIAS_CE and t is not None and (t.dtype != torch.bfloat16 or t.shape != out.shape
+                                                          or t.stride() != out.stride()):
+            raise RuntimeError("gemm: %s must be bf16 and laid out like out" % nm)
+    d.bias, d.out2, d.aux, d.colsum = _p(bias), _p(out2), _p(aux), _p(colsum)
+    d.ldp, d.ldq, d.ldo = P.stride(0), ldq, ldo
+    d.q_rpb, d.q_bstride, d.o_rpb, d.o_bstride = q_rpb, q_bs, o_rpb, o_bs
+    d.accum = int(bool(pr.get("accum", False)))
+    # (Kc given: a contraction longer than the K-contiguous operand's rows -- its partner is zero-padded)
+    d.Ni, d.Nj, d.Kc = Ni, Nj, int(pr.get("Kc", Kc))
+    d.p_bytes, d.q_bytes, d.ksplit = int(pr.get("p_bytes", 0)), int(pr.get("q_bytes", 0)), int(pr.get("ksplit", 1))
+    return gemm_route.Shape(Ni, Nj, d.Kc, colsum is not None, bool(q_rpb or o_rpb))
+
+
+def _gemm_grouped_launch(problems, flags, epilogue, tile):
     n = len(problems)
     arr = (_GemmDesc * n)()
-    t_auto = 32
-    any_map = False
-    for k, pr in enumerate(problems):
-        P, Q, out = _mat(pr["P"], "P"), pr["Q"], pr["out"]
-        qshape, ldq, q_rpb, q_bs = _mat_rows(Q, "Q")
-        oshape, ldo, o_rpb, o_bs = _mat_rows(out, "out")
-        any_map = any_map or bool(q_rpb or o_rpb)
-        if P.dtype != torch.bfloat16 or Q.dtype != torch.bfloat16:
-            raise RuntimeError("gemm: operands must be bf16")
-        if out.dtype != (torch.float32 if f32 else torch.bfloat16):
-            raise RuntimeError("gemm: out must be %s" % ("float32" if f32 else "bfloat16"))
-        Ni, Kc = (P.shape[1], P.shape[0]) if pxc else (P.shape[0], P.shape[1])
-        Nj, Kq = (qshape[1], qshape[0]) if qxc else (qshape[0], qshape[1])
-        Ni = int(pr.get("Ni", Ni))  # output wider than P's rows (padded vocabulary): P's true extent goes in p_bytes
-        if (Kq != Kc and "Kc" not in pr) or tuple(oshape) != (Nj, Ni):
-            raise RuntimeError("gemm: shape mismatch P%s Q%s out%s" % (tuple(P.shape), tuple(Q.shape), tuple(out.shape)))
-        d = arr[k]
-        d.P, d.Q, d.out = P.data_ptr(), Q.data_ptr(), out.data_ptr()
-        bias, out2, aux, colsum = pr.get("bias"), pr.get("out2"), pr.get("aux"), pr.get("colsum")
-        if bias is not None and (bias.dtype not in (torch.float32, torch.bfloat16) or bias.numel() != Ni
-                                 or not bias.is_contiguous()):
-            raise RuntimeError("gemm: bias must be a contiguous fp32 or bf16 (Ni,) tensor")
-        d.bias_bf16 = int(bias is not None and bias.dtype == torch.bfloat16)
-        # (weight-gradient form: colsum (Nj,) receives the column sums of Q over the contraction; with ksplit > 1 it is
-        # accumulated with atomics and must arrive zeroed)
-        n_cs = Nj if (pxc and qxc and f32) else Ni
-        if epilogue != EPI_BIAS_CE and colsum is not None and (colsum.dtype != torch.float32 or colsum.numel() != n_cs
-                                                               or not colsum.is_contiguous()):
-            raise RuntimeError("gemm: colsum must be a contiguous fp32 (%d,) tensor" % n_cs)
-        for t, nm in ((out2, "out2"), (aux, "aux")):
-            if epilogue != EPI_BIAS_CE and t is not None and (t.dtype != torch.bfloat16 or t.shape != out.shape
-                                                              or t.stride() != out.stride()):
-                raise RuntimeError("gemm: %s must be bf16 and laid out like out" % nm)
-        d.bias, d.out2, d.aux, d.colsum = _p(bias), _p(out2), _p(aux), _p(colsum)
-        d.ldp, d.ldq, d.ldo = P.stride(0), ldq, ldo
-        d.q_rpb, d.q_bstride, d.o_rpb, d.o_bstride = q_rpb, q_bs, o_rpb, o_bs
-        d.accum = int(bool(pr.get("accum", False)))
-        d.Ni, d.Nj, d.Kc = Ni, Nj, Kc
-        d.p_bytes, d.q_bytes, d.ksplit = int(pr.get("p_bytes", 0)), int(pr.get("q_bytes", 0)), int(pr.get("ksplit", 1))
-        if "Kc" in pr:  # contraction longer than the K-contiguous operand's rows (its partner is zero-padded)
-            d.Kc = int(pr["Kc"])
-        # (the 256 x 128 kernel also has a weight-gradient form -- tile=128 on request: measured equal to the 256 x 256 kernel
-        # alone and slower inside the step, so it is never the automatic choice)
-        mid_ok = (not qxc and not f32 and d.Kc >= 128 and colsum is None
-                  and epilogue in (EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_ADD))
-        all_mid_ok = mid_ok if k == 0 else (all_mid_ok and mid_ok)
-        t_auto = max(t_auto, pick_tile(Ni, Nj, qxc, True))
-    if t_auto == 128 and not all_mid_ok:
-        t_auto = 256   # (one tile class per launch: every problem of the group must be able to take the 256 x 128 kernel)
-    if (t_auto == 128 and TILE256_MIN_K[0] and not pxc and epilogue in (EPI_NONE, EPI_BIAS)
-            and all(int(arr[k].Kc) >= TILE256_MIN_K[0] for k in range(n))):
-        t_auto = 256   # (long contractions: TILE256_MIN_K above)
-    if t_auto == 256 and any_map and tile is None and not (pxc and qxc and f32):
-        t_auto = 64    # (the 256 x 256 kernel maps only the contraction rows of its weight-gradient form)
+    shapes = [_gemm_pack(arr[k], pr, flags, epilogue) for k, pr in enumerate(problems)]
+    tile = int(tile or gemm_route.auto_tile(shapes, flags, epilogue))
     dev = problems[0]["out"].device
-    if (tile or t_auto) != 128:
+    if tile != 128:
         flags &= ~GEMM_BACKGROUND   # (only the persistent 256 x 128 kernel has a reduced grid)
     with torch.cuda.device(dev):
-        if (tile or t_auto) == 128 and n == 1 and (STREAMK[0] or STREAMK256[0]):
+        if tile == 128 and n == 1 and (STREAMK[0] or STREAMK256[0]):
             _streamk_workspace(dev)
-        _check(_lib.bq_gemm_bf16(arr, n, int(flags), int(epilogue), int(tile or t_auto), _stream()), "gemm_bf16")
+        _check(_lib.bq_gemm_bf16(arr, n, int(flags), int(epilogue), tile, _stream()), "gemm_bf16")
 
 
 def _gemm_grouped_det(problems, flags, epilogue, tile):

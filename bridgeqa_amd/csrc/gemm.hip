@@ -1244,126 +1244,76 @@ __global__ __launch_bounds__(256) void splitk_fold_det_kernel(const float *__res
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-// long_k: every problem of the launch has >= 12 K tiles and the launch is small (host decision in launch_gemm):
-// the bf16-output small-tile forms then run two K tiles per pipeline step
-template <bool P_XC, bool Q_XC, int EPI, bool OUT_F32>
-static int launch_variant(const GemmArgs &ga, int tile, hipStream_t st, bool long_k = false) {
-  constexpr bool KT2_OK = !OUT_F32 && !Q_XC && EPI != EPI_BIAS_CE;
-  if (tile == 256) {
-    // (the K-contiguous dX forms -- a pre-transposed weight, csrc/transpose.hip -- exist for the small tiles and 256 x 128)
-    if constexpr (P_XC || (EPI != EPI_DGELU && EPI != EPI_ADD))
+// Outside gemm_form() (gemm_common.h) a launcher returns -1 and instantiates nothing.  long_k: every problem of the launch has
+// >= 12 K tiles and the launch is small (launch_gemm): the bf16-output small-tile forms then run two K tiles per pipeline step.
+// KIND = FORM_DET (BQ_GEMM_DET): the fp32-output forms of the small-tile kernel (the only ones with float atomics: cut
+// contractions, accum) run on gemm64_kernel_det; every other form the deterministic mode may launch stores plainly
+// (bf16-output column sums and stream-K are refused by bq_gemm_bf16)
+template <bool P_XC, bool Q_XC, int EPI, bool OUT_F32, int KIND = FORM_PLAIN>
+static int launch_variant(const GemmArgs &ga, int tile, hipStream_t st, bool long_k) {
+  constexpr bool KT2_OK = !OUT_F32 && !Q_XC;
+  int rc = -1;
+  with_int<256, 64, 32>(tile, [&](auto T) {
+    constexpr int TJ = decltype(T)::value;
+    if constexpr (!gemm_form(TJ, P_XC, Q_XC, OUT_F32, EPI, KIND)) {
+      return;
+    } else if constexpr (KIND == FORM_DET) {
+      hipLaunchKernelGGL((gemm64_kernel_det<TJ, P_XC, Q_XC, EPI>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
+    } else if constexpr (TJ == 256) {
       hipLaunchKernelGGL((gemm256_kernel<P_XC, Q_XC, EPI, OUT_F32>), dim3(ga.total_tiles), dim3(512), 0, st, ga);
-    else
-      return -1;
-  } else if (tile == 64) {
-    if constexpr (KT2_OK) {
-      if (long_k) {
-        hipLaunchKernelGGL((gemm64_kernel<64, P_XC, Q_XC, EPI, OUT_F32, 2>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
-        return 0;
-      }
-    }
-    hipLaunchKernelGGL((gemm64_kernel<64, P_XC, Q_XC, EPI, OUT_F32>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
-  } else {
-    if constexpr (!Q_XC) {
-      if constexpr (KT2_OK) {
-        // four K tiles per step (144 KB of LDS: one workgroup per CU) for launches of <= 512 tiles: c3 45.05 -> 44.57 ms
-        constexpr int k4_tiles = 12;
-        bool k4 = long_k && k4_tiles > 0 && ga.total_tiles <= 512;
-        for (int k = 0; k < ga.n; ++k) k4 = k4 && ga.p[k].Kc >= 64 * k4_tiles;
-        if (k4) {
-          hipLaunchKernelGGL((gemm64_kernel<32, P_XC, Q_XC, EPI, OUT_F32, 4>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
-          return 0;
-        }
-        if (long_k) {
-          hipLaunchKernelGGL((gemm64_kernel<32, P_XC, Q_XC, EPI, OUT_F32, 2>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
-          return 0;
-        }
-      }
-      hipLaunchKernelGGL((gemm64_kernel<32, P_XC, Q_XC, EPI, OUT_F32>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
     } else {
-      return -1;
+      // four K tiles per step (144 KB of LDS: one workgroup per CU) for launches of <= 512 32-row tiles: c3 45.05 -> 44.57 ms
+      constexpr int k4_tiles = 12;
+      bool k4 = KT2_OK && TJ == 32 && long_k && k4_tiles > 0 && ga.total_tiles <= 512;
+      for (int k = 0; k < ga.n; ++k) k4 = k4 && ga.p[k].Kc >= 64 * k4_tiles;
+      with_int<4, 2, 1>(k4 ? 4 : (KT2_OK && long_k) ? 2 : 1, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        if constexpr (KT == 1 || (KT2_OK && (KT == 2 || TJ == 32)))
+          hipLaunchKernelGGL((gemm64_kernel<TJ, P_XC, Q_XC, EPI, OUT_F32, KT>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
+      });
     }
-  }
-  return 0;
-}
-
-// BQ_GEMM_DET: the fp32-output forms of the small-tile kernel (the only ones with float atomics: cut contractions, accum) run
-// on gemm64_kernel_det; every other form the deterministic mode may launch stores plainly (bf16-output column sums and
-// stream-K are refused by bq_gemm_bf16)
-template <bool P_XC, bool Q_XC, int EPI>
-static int launch_det_variant(const GemmArgs &ga, int tile, hipStream_t st) {
-  if (tile == 64) {
-    hipLaunchKernelGGL((gemm64_kernel_det<64, P_XC, Q_XC, EPI>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
-    return 0;
-  }
-  if constexpr (!Q_XC) {
-    hipLaunchKernelGGL((gemm64_kernel_det<32, P_XC, Q_XC, EPI>), dim3(ga.total_tiles), dim3(256), 0, st, ga);
-    return 0;
-  }
-  return -1;
+    rc = 0;
+  });
+  return rc;
 }
 
 static int launch_gemm(const GemmArgs &ga, int flags, int epi, int tile, hipStream_t st) {
   const bool pxc = flags & BQ_GEMM_P_XC, qxc = flags & BQ_GEMM_Q_XC, f32 = flags & BQ_GEMM_OUT_F32;
-  if ((flags & BQ_GEMM_DET) && f32 && tile != 256 && tile != 128) {
-    if (!pxc && !qxc && epi == EPI_NONE) return launch_det_variant<false, false, EPI_NONE>(ga, tile, st);
-    if (!pxc && !qxc && epi == EPI_BIAS) return launch_det_variant<false, false, EPI_BIAS>(ga, tile, st);
-    if (pxc && !qxc && epi == EPI_NONE) return launch_det_variant<true, false, EPI_NONE>(ga, tile, st);
-    if (pxc && qxc && epi == EPI_NONE) return launch_det_variant<true, true, EPI_NONE>(ga, tile, st);
-    return -1;
-  }
-  // measured on the c3 step (A/B in one call): never 46.2 ms, from 24 K tiles 45.5-45.9, from 12 K tiles 45.3-45.6
-  constexpr int long_k_tiles = 12;
-  bool long_k = long_k_tiles > 0 && tile != 256 && ga.total_tiles <= 2048;
-  for (int k = 0; k < ga.n; ++k) long_k = long_k && ga.p[k].Kc >= 64 * long_k_tiles;
   if (tile == 128 && (gemm_sk_mode() & 2) && !(flags & (BQ_GEMM_BACKGROUND | BQ_GEMM_DET)) && ga.n == 1 && !pxc && !qxc && !f32 &&
       (epi == EPI_NONE || epi == EPI_BIAS) && ga.p[0].colsum == nullptr && ga.p[0].q_rpb() == 0 && ga.p[0].o_rpb() == 0) {
     // stream-K on the 256 x 256 kernel (header of gemm256_kernel): one problem with a long contraction whose 256 x 256 tiles
     // would leave >= 15 % of a one-workgroup-per-CU grid idle, every share still >= 16 K tiles
     const GemmProblem &p0 = ga.p[0];
-    const int cus = device_cus();
-    const int nkt = (p0.Kc + 63) >> 6, tiles = ((p0.Ni + 255) / 256) * ((p0.Nj + 255) / 256);
-    const long units = (long)tiles * nkt;
-    const int rounds = (tiles + cus - 1) / cus;
+    const int cus = device_cus(), tiles = ((p0.Ni + 255) / 256) * ((p0.Nj + 255) / 256);
     long ws_bytes = 0;
     void *ws = gemm_sk_workspace(st, &ws_bytes);
-    if (ws != nullptr && nkt >= 24 && tiles >= cus / 2 && units / cus >= 16 && (long)rounds * nkt * cus >= units * 115 / 100 &&
-        8L * tiles <= SK_TICKET_BYTES && ws_bytes >= SK_TICKET_BYTES + 2L * cus * 256 * 256 * 4) {
+    if (streamk_fits((p0.Kc + 63) >> 6, tiles, cus, 256L * 256 * 4, ws, ws_bytes)) {
       GemmArgs g2 = ga;
       g2.sk_ws = ws;
       g2.total_tiles = tiles;
       g2.p[0].tile0 = 0;
       g2.p[0].tiles_ks = (p0.Ni + 255) / 256;   // tiles along i, no K split
-      if (epi == EPI_NONE) hipLaunchKernelGGL((gemm256_kernel<false, false, EPI_NONE, false, true>), dim3(cus), dim3(512), 0, st, g2);
-      else hipLaunchKernelGGL((gemm256_kernel<false, false, EPI_BIAS, false, true>), dim3(cus), dim3(512), 0, st, g2);
+      with_int<EPI_NONE, EPI_BIAS>(epi, [&](auto E) {
+        static_assert(gemm_form(256, false, false, false, decltype(E)::value, FORM_STREAMK), "not a stream-K form");
+        hipLaunchKernelGGL((gemm256_kernel<false, false, decltype(E)::value, false, true>), dim3(cus), dim3(512), 0, st, g2);
+      });
       return 0;
     }
   }
   if (tile == 128)  // csrc/gemm_mid.hip: forward / dX (bf16 out, K-contiguous Q) and the weight-gradient form
     return launch_gemm_mid(ga, pxc, qxc, f32, epi, (flags & BQ_GEMM_BACKGROUND) != 0, st);
-  if (!pxc && !qxc && !f32) {
-    if (epi == EPI_NONE) return launch_variant<false, false, EPI_NONE, false>(ga, tile, st, long_k);
-    if (epi == EPI_BIAS) return launch_variant<false, false, EPI_BIAS, false>(ga, tile, st, long_k);
-    if (epi == EPI_BIAS_GELU) return launch_variant<false, false, EPI_BIAS_GELU, false>(ga, tile, st, long_k);
-    if (epi == EPI_DGELU) return launch_variant<false, false, EPI_DGELU, false>(ga, tile, st, long_k);
-    if (epi == EPI_ADD) return launch_variant<false, false, EPI_ADD, false>(ga, tile, st, long_k);
-    if (epi == EPI_BIAS_CE && tile == 256) {
-      hipLaunchKernelGGL((gemm256_kernel<false, false, EPI_BIAS_CE, false>), dim3(ga.total_tiles), dim3(512), 0, st, ga);
-      return 0;
-    }
-  } else if (!pxc && !qxc && f32) {  // forward with fp32 results (the detector's regression heads: 64 / 32 tiles)
-    if (epi == EPI_NONE && tile != 256) return launch_variant<false, false, EPI_NONE, true>(ga, tile, st);
-    if (epi == EPI_BIAS && tile != 256) return launch_variant<false, false, EPI_BIAS, true>(ga, tile, st);
-  } else if (pxc && !qxc && f32) {
-    if (epi == EPI_NONE && tile != 256) return launch_variant<true, false, EPI_NONE, true>(ga, tile, st);
-  } else if (pxc && !qxc && !f32) {
-    if (epi == EPI_NONE) return launch_variant<true, false, EPI_NONE, false>(ga, tile, st, long_k);
-    if (epi == EPI_DGELU) return launch_variant<true, false, EPI_DGELU, false>(ga, tile, st, long_k);
-    if (epi == EPI_ADD) return launch_variant<true, false, EPI_ADD, false>(ga, tile, st, long_k);
-  } else if (pxc && qxc && f32) {
-    if (epi == EPI_NONE) return launch_variant<true, true, EPI_NONE, true>(ga, tile, st);
-  }
-  return -1;
+  const bool det = (flags & BQ_GEMM_DET) && f32 && tile != 256;
+  // measured on the c3 step (A/B in one call): never 46.2 ms, from 24 K tiles 45.5-45.9, from 12 K tiles 45.3-45.6
+  constexpr int long_k_tiles = 12;
+  bool long_k = long_k_tiles > 0 && tile != 256 && ga.total_tiles <= 2048;
+  for (int k = 0; k < ga.n; ++k) long_k = long_k && ga.p[k].Kc >= 64 * long_k_tiles;
+  int rc = -1;
+  with_gemm_form(pxc, qxc, f32, epi, [&](auto PX, auto QX, auto F32, auto E) {
+    constexpr bool P = decltype(PX)::value, Q = decltype(QX)::value, F = decltype(F32)::value;
+    constexpr int EP = decltype(E)::value;
+    rc = det ? launch_variant<P, Q, EP, F, FORM_DET>(ga, tile, st, false) : launch_variant<P, Q, EP, F>(ga, tile, st, long_k);
+  });
+  return rc;
 }
 
 }  // namespace bq
@@ -1372,6 +1322,8 @@ extern "C" int bq_gemm_max_problems(void) { return bq::GEMM_MAX_PROBLEMS; }
 
 extern "C" int bq_gemm_bf16(const bq_gemm_desc *d, int n, int flags, int epilogue, int tile, void *stream) {
   using namespace bq;
+  // (first: the launchers dispatch on the epilogue with with_int, which runs its last value when none matches)
+  BQ_REQUIRE(epilogue >= BQ_GEMM_EPI_NONE && epilogue <= BQ_GEMM_EPI_ADD, BQ_EINVAL, "bq_gemm_bf16: unknown epilogue %d", epilogue);
   BQ_REQUIRE(d != nullptr && n >= 1, BQ_EINVAL, "bq_gemm_bf16: no problems");
   BQ_REQUIRE(tile == 256 || tile == 128 || tile == 64 || tile == 32, BQ_EINVAL,
              "bq_gemm_bf16: tile must be 256, 128 (= 256 x 128), 64 or 32 (got %d)", tile);

@@ -15,11 +15,10 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;
 typedef __attribute__((address_space(3))) void lds_void_t;
 
 enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_DGELU = 3, EPI_BIAS_CE = 4, EPI_ADD = 5 };
-enum { GF_P_XC = 1, GF_Q_XC = 2, GF_OUT_F32 = 4, GF_ACCUM = 8 };
 
 struct GemmProblem {
   const __bf16 *P, *Q;
-  void *out;           // out[j * ldo + i]: bf16, or fp32 with GF_OUT_F32
+  void *out;           // out[j * ldo + i]: bf16, or fp32 with BQ_GEMM_OUT_F32
   const void *bias;    // over i (EPI_BIAS / EPI_BIAS_GELU) or null: fp32, or bf16 when bias_bf16
   void *out2;          // EPI_BIAS_GELU: gelu(out) as bf16, same layout as out
   const __bf16 *aux;   // EPI_DGELU: the pre-activation y[j][i] (ld = ldo): out = acc * gelu'(y); EPI_ADD: out = acc + aux[j][i]
@@ -80,6 +79,46 @@ struct GemmArgs {
 };
 constexpr long SK_TICKET_BYTES = 65536, SK_SLAB_BYTES = 256 * 128 * 4;
 static_assert(sizeof(GemmArgs) <= 4096, "kernel-argument limit");
+
+// ---- the forms that exist (host) --------------------------------------------------------------------------------------------
+// True exactly for the instantiations the library may launch: gemm256_kernel (tile 256), gemm128_kernel (128), gemm64_kernel
+// (64 / 32; its K tiles per step are a run-time choice of the launcher, not a form), gemm64_kernel_det (FORM_DET) and the two
+// stream-K forms.  The launchers instantiate only under it; tests/gemm_ref.py ROUTE_TABLE restates it (compared on the CPU).
+enum { FORM_PLAIN = 0, FORM_DET = 1, FORM_STREAMK = 2 };
+constexpr bool gemm_form(int tile, bool p_xc, bool q_xc, bool out_f32, int epi, int kind = FORM_PLAIN) {
+  const bool large = tile == 256 || tile == 128;
+  if (kind == FORM_STREAMK)   // one K-contiguous bf16 problem; the residual add only on the 256 x 128 tile
+    return large && !p_xc && !q_xc && !out_f32 && (epi == EPI_NONE || epi == EPI_BIAS || (epi == EPI_ADD && tile == 128));
+  if (p_xc && q_xc)           // the weight gradient: fp32 out; fixed-order on the 64-row tile only
+    return out_f32 && epi == EPI_NONE && (kind == FORM_DET ? tile == 64 : tile != 32);
+  if (q_xc) return false;
+  if (out_f32)                // fp32 results and cut contractions: the small tiles, atomic or fixed-order
+    return !large && (epi == EPI_NONE || (epi == EPI_BIAS && !p_xc));
+  if (kind == FORM_DET) return false;   // (bf16 outputs store plainly in every mode)
+  if (epi == EPI_BIAS_CE) return tile == 256 && !p_xc;   // the LM-head cross-entropy epilogue
+  // forward, and dX: a contraction-major P, or K-contiguous DGELU / ADD on a pre-transposed weight (not on tile 256)
+  if (p_xc) return epi == EPI_NONE || epi == EPI_DGELU || epi == EPI_ADD;
+  return epi == EPI_NONE || epi == EPI_BIAS || epi == EPI_BIAS_GELU || (tile != 256 && (epi == EPI_DGELU || epi == EPI_ADD));
+}
+// f(P_XC, Q_XC, OUT_F32, EPI) as integral constants (bq_gemm_bf16 checks epi: with_int runs its last value when none matches)
+template <class F>
+inline void with_gemm_form(bool p_xc, bool q_xc, bool out_f32, int epi, F &&f) {
+  with_flags(p_xc, q_xc, [&](auto PX, auto QX) {
+    with_flag(out_f32, [&](auto F32) {
+      with_int<EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_CE, EPI_ADD>(epi, [&](auto E) { f(PX, QX, F32, E); });
+    });
+  });
+}
+
+// stream-K instead of whole tiles (both large kernels): a registered workspace that holds the tickets and two slabs per slot,
+// and whole tiles would leave >= 15 % of a `slots`-workgroup grid's makespan idle while a share is still >= 16 K tiles (the
+// hand-off moves one slab per cut: ~1/3 of a 48-K-tile share's gain at 36 K tiles, more than the gain of a 12-K-tile contraction)
+inline bool streamk_fits(int nkt, int tiles, int slots, long slab_bytes, const void *ws, long ws_bytes) {
+  const long units = (long)tiles * nkt;
+  const int rounds = (tiles + slots - 1) / slots;
+  return ws != nullptr && nkt >= 24 && tiles >= slots / 2 && units / slots >= 16 && (long)rounds * nkt * slots >= units * 115 / 100 &&
+         8L * tiles <= SK_TICKET_BYTES && ws_bytes >= SK_TICKET_BYTES + 2L * slots * slab_bytes;
+}
 
 // ---- LDS images -----------------------------------------------------------------------------------------------------
 // KC unit: [64 rows][64 k] bf16, 128-B rows, 16-B chunk ch of row r at r*128 + ((ch ^ (r & 7)) << 4)

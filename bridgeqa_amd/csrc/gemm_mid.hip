@@ -606,7 +606,6 @@ int gemm_sk_mode() {
   }
   return env_off ? 0 : g_sk_mode;
 }
-static bool sk_enabled() { return (gemm_sk_mode() & 1) != 0; }
 
 int launch_gemm_mid(const GemmArgs &ga_in, bool p_xc, bool q_xc, bool out_f32, int epi, bool background, hipStream_t stream) {
   const int slots = 2 * device_cus();   // two co-resident workgroups per CU (64 KB of LDS, <= 256 VGPRs each)
@@ -616,55 +615,36 @@ int launch_gemm_mid(const GemmArgs &ga_in, bool p_xc, bool q_xc, bool out_f32, i
   ga.sk_ws = nullptr;
   // stream-K (header): one problem, a K-contiguous P (forward, or dX on the transposed weight copy), bf16 out, a long
   // contraction cut across a grid that whole tiles would fill unevenly -- the N = 768 / K = 3072 launches of the ViT MLP
-  if (sk_enabled() && !background && ga.n == 1 && !p_xc && !q_xc && !out_f32 && (epi == EPI_NONE || epi == EPI_BIAS || epi == EPI_ADD)) {
-    const int nkt = (ga.p[0].Kc + 63) >> 6, tiles = ga.total_tiles;
-    const long units = (long)tiles * nkt;
-    const int rounds = (tiles + slots - 1) / slots;
+  if ((gemm_sk_mode() & 1) && !background && ga.n == 1 && !p_xc && !q_xc && !out_f32 && (epi == EPI_NONE || epi == EPI_BIAS || epi == EPI_ADD)) {
     long ws_bytes = 0;
     void *ws = gemm_sk_workspace(stream, &ws_bytes);
-    // worth it when whole tiles leave >= 15 % of the makespan idle and a share is still >= 16 K tiles (the hand-off moves
-    // 128 KB per cut: ~1/3 of a 48-K-tile share's gain at 36 K tiles, more than the gain of a 12-K-tile contraction)
-    if (ws != nullptr && nkt >= 24 && tiles >= slots / 2 && units / slots >= 16 && (long)rounds * nkt * slots >= units * 115 / 100
-        && 8L * tiles <= SK_TICKET_BYTES && ws_bytes >= SK_TICKET_BYTES + 2L * slots * SK_SLAB_BYTES) {
+    if (streamk_fits((ga.p[0].Kc + 63) >> 6, ga.total_tiles, slots, SK_SLAB_BYTES, ws, ws_bytes)) {
       ga.sk_ws = ws;
-      const dim3 grid(slots), block(256);
-      if (epi == EPI_NONE) hipLaunchKernelGGL((gemm128_kernel<false, false, EPI_NONE, false, 16, true>), grid, block, 0, stream, ga);
-      else if (epi == EPI_BIAS) hipLaunchKernelGGL((gemm128_kernel<false, false, EPI_BIAS, false, 16, true>), grid, block, 0, stream, ga);
-      else hipLaunchKernelGGL((gemm128_kernel<false, false, EPI_ADD, false, 16, true>), grid, block, 0, stream, ga);
+      with_int<EPI_NONE, EPI_BIAS, EPI_ADD>(epi, [&](auto E) {
+        static_assert(gemm_form(128, false, false, false, decltype(E)::value, FORM_STREAMK), "not a stream-K form");
+        hipLaunchKernelGGL((gemm128_kernel<false, false, decltype(E)::value, false, 16, true>), dim3(slots), dim3(256), 0, stream, ga);
+      });
       return 0;
     }
   }
+  // (a bf16 output takes no column sums here; the weight-gradient form -- fp32 out -- does, on request)
+  for (int k = 0; k < ga.n; ++k)
+    if (!out_f32 && ga.p[k].colsum != nullptr) return -1;
   // background: one workgroup per CU (BQ_GEMM_BACKGROUND, include/bqhip_fusion.h)
   const int use = background ? (slots + 1) / 2 : slots;
   const dim3 grid(ga.total_tiles < use ? ga.total_tiles : use), block(256);
   // output stores write-through (sc1): the lines are dropped from the XCD's L2, which then keeps the weight / activation
   // panels the co-scheduled tiles share.  MEASURED against the default policy, every c3 shape: 3-9 % faster (qkv 60.5 ->
   // 59.7 us, proj 26.6 -> 24.2, fc1 + GELU 104.5 -> 99.9, dX qkv 60.4 -> 57.3)
-#define BQ_MID_LAUNCH(PX, E)                                                                                        \
-  do {                                                                                                              \
-    hipLaunchKernelGGL((gemm128_kernel<PX, false, E, false, 16>), grid, block, 0, st_, ga);                         \
-    return 0;                                                                                                       \
-  } while (0)
-  hipStream_t st_ = stream;
-  if (q_xc || out_f32) {   // the weight-gradient form (fp32 out, column sums on request)
-    if (!(p_xc && q_xc && out_f32 && epi == EPI_NONE)) return -1;
-    hipLaunchKernelGGL((gemm128_kernel<true, true, EPI_NONE, true, 16>), grid, block, 0, st_, ga);
-    return 0;
-  }
-  for (int k = 0; k < ga.n; ++k)
-    if (ga.p[k].colsum != nullptr) return -1;
-  if (!p_xc) {
-    if (epi == EPI_NONE) BQ_MID_LAUNCH(false, EPI_NONE);
-    if (epi == EPI_BIAS) BQ_MID_LAUNCH(false, EPI_BIAS);
-    if (epi == EPI_BIAS_GELU) BQ_MID_LAUNCH(false, EPI_BIAS_GELU);
-    if (epi == EPI_DGELU) BQ_MID_LAUNCH(false, EPI_DGELU);
-    if (epi == EPI_ADD) BQ_MID_LAUNCH(false, EPI_ADD);
-  } else {
-    if (epi == EPI_NONE) BQ_MID_LAUNCH(true, EPI_NONE);
-    if (epi == EPI_DGELU) BQ_MID_LAUNCH(true, EPI_DGELU);
-    if (epi == EPI_ADD) BQ_MID_LAUNCH(true, EPI_ADD);
-  }
-  return -1;
+  int rc = -1;
+  with_gemm_form(p_xc, q_xc, out_f32, epi, [&](auto PX, auto QX, auto F32, auto E) {
+    if constexpr (gemm_form(128, decltype(PX)::value, decltype(QX)::value, decltype(F32)::value, decltype(E)::value)) {
+      hipLaunchKernelGGL((gemm128_kernel<decltype(PX)::value, decltype(QX)::value, decltype(E)::value, decltype(F32)::value, 16>),
+                         grid, block, 0, stream, ga);
+      rc = 0;
+    }
+  });
+  return rc;
 }
 
 }  // namespace bq

@@ -950,7 +950,7 @@ class _TwinKVFn(torch.autograd.Function):
                 db = torch.empty(ga.shape[-1], dtype=torch.float32, device=hs.device)
                 f = _ext.GEMM_P_XC | _ext.GEMM_Q_XC | _ext.GEMM_OUT_F32
                 _ext.gemm_grouped([dict(P=xa, Q=ga, out=dw, colsum=db)], f, _ext.EPI_NONE,
-                                  256 if (B * ga.shape[1] >= _BIG_ROWS and ga.shape[1] >= 64) else 64)
+                                  256 if (wgrad_class(B * ga.shape[1]) == "big" and ga.shape[1] >= 64) else 64)
                 # (accum: ONE adder per element onto what the launch above stored on this stream -- bitwise reproducible as
                 # it is, also in the deterministic mode, which runs it with plain loads and stores)
                 _ext.gemm_grouped([dict(P=xb, Q=gb, out=dw, colsum=db, accum=True)], f, _ext.EPI_NONE, 64)

@@ -9,6 +9,9 @@ import torch.nn.functional as F
 
 from .fusion_state import *  # noqa: F401,F403
 from .fusion_state import __all__ as _state_all
+# the weight-gradient tile classes live beside the GEMM tile policy; the cells keep their names here (tools flip them)
+from .gemm_route import DW_TILE as _DW_TILE, SHORT_DW_MIN_ROWS as _SHORT_DW_MIN_ROWS  # noqa: F401
+from .gemm_route import SHORT_DW_TILE as _SHORT_DW_TILE, wgrad_class
 
 # ---- native GEMMs (csrc/gemm.hip through _ext.gemm_*) ------------------------------------------------------------
 # Every nn.Linear of the fusion half on the bf16 CUDA path: forward (+bias, +GELU), input gradient (+GELU derivative,
@@ -59,7 +62,7 @@ def _dw_db(g2, x2, need_dw, need_db):
     if need_dw:
         if native:
             from . import _ext
-            dw = _ext.gemm_dw(_rows(g2), _rows(x2), tile=256 if g2.shape[0] >= _BIG_ROWS else 64)
+            dw = _ext.gemm_dw(_rows(g2), _rows(x2), tile=256 if wgrad_class(g2.shape[0]) == "big" else 64)
         else:
             dw = _mm_f32(g2.t(), x2)
     if need_db:
@@ -78,8 +81,6 @@ def _dw_db(g2, x2, need_dw, need_db):
 # 256 x 256 with the full 16400-row contraction each -- instead of 48 launches of 27-36 tiles) and ALL bias gradients
 # with one grouped column-sum launch.  MI355X has the HBM for it: the parked dY of config c3 are 2.7 GB.
 _DEFER = [None]
-_BIG_ROWS = 1024  # contractions at least this long run on the 256 x 256 kernel (measured: sending the text side's 160-640-row
-                  # contractions there too costs +1.5 ms per c3 step -- its pipeline fill and 256 KB fp32 tile epilogue dominate)
 
 
 def begin_deferred_wgrad():
@@ -112,14 +113,6 @@ _PLAN_CACHE = {}
 _PLAN_WGRAD = [True]
 _QSUM = [True]
 _QSUM64 = [True]
-_DW_TILE = [256]   # 256: gemm256_kernel (one workgroup per CU); 128: the 256 x 128 persistent kernel's weight-gradient form
-_SHORT_DW_MIN_ROWS = [64]    # contractions from this many rows on (the decoder's B x 5 answer rows = 80 included: the flush 0.53 -> 0.48 ms,
-                             # bit-identical; the 256 x 128 form, _SHORT_DW_TILE = 128, needs >= 128)
-_SHORT_DW_TILE = [256]  # short contractions (128 <= rows < 1024: the text side's B x 20 token rows): 256 = gemm256_kernel (since
-                        # round 6's K loop: the 228 problems of one flush 0.52 ms against 0.59 on the persistent 256 x 128
-                        # kernel's weight-gradient form and 0.77 on the 64 x 64-tile kernel, tools/bench_short_dw.py, each form
-                        # graph-replayed and interleaved, bit-identical results; c3 step 31.31 -> 31.17 ms over five interleaved
-                        # pairs, profiles/r06_short_dw_tile.txt); 128 and 64 select the other two
 
 
 def plan_big_launches(tiles, cus, max_problems=36, moved_cost=0.011):
@@ -190,8 +183,11 @@ def flush_deferred_items(items):
     dws = [None] * len(items)
     prim = [k for k, it in enumerate(items) if it[4] is None]
     second = [k for k, it in enumerate(items) if it[4] is not None]
-    big = [k for k in prim if _nrows(items[k][0]) >= _BIG_ROWS]
-    small = [k for k in prim if _nrows(items[k][0]) < _BIG_ROWS]
+    # (mid = only the SHORT contractions: the planner's moved problems below -- full 16 400-row contractions of 9 tiles --
+    # stay on the 64-tile kernel, whose cut contraction spreads them over the chip: the 256 x 128 form ran them at 5 % MFMA busy)
+    cls = {k: wgrad_class(_nrows(items[k][0]), (items[k][0].shape[-1], items[k][1].shape[-1], items[k][0].dim() == 2))
+           for k in prim}
+    big, mid, small = ([k for k in prim if cls[k] == c] for c in ("big", "mid", "small"))
     if _PLAN_WGRAD[0]:
         # longest contractions first: a launch's workgroups start in tile order, so the long tiles (16 720-row image
         # tokens) run from the beginning and the short ones (4 416-row object tokens) fill in behind them (A/B x4: 40.88 vs
@@ -206,15 +202,6 @@ def flush_deferred_items(items):
         groups = [[big[j] for j in g] for g in plan_groups]
         small = small + [big[j] for j in moved]
     dbs = {}
-    mid = []
-    if _SHORT_DW_TILE[0] in (128, 256):
-        min_rows = max(_SHORT_DW_MIN_ROWS[0], 128 if _SHORT_DW_TILE[0] == 128 else 1)
-        # (only the SHORT contractions: the planner's moved problems -- full 16 400-row contractions of 9 tiles -- stay on
-        # the 64-tile kernel, whose cut contraction spreads them over the chip: the 256 x 128 form ran them at 5 % MFMA busy)
-        ok = lambda it: (min_rows <= _nrows(it[0]) < _BIG_ROWS and it[0].dim() == 2 and it[0].shape[-1] >= 128
-                         and it[1].shape[-1] >= 256)
-        mid = [k for k in small if ok(items[k])]
-        small = [k for k in small if not ok(items[k])]
     for tile, idx_groups in ((_DW_TILE[0], groups), (_SHORT_DW_TILE[0], [mid] if mid else []), (64, [small] if small else [])):
         for idx in idx_groups:
             probs = []

@@ -33,10 +33,11 @@ Non-linear epilogues, constants from csrc/gemm_common.h (fit and scan: DESIGN.md
     column sums of the weight-gradient form (colsum[j] = sum_k Q[j][k], from all-ones MFMAs): Kc u sum_k |Q[j][k]| x 2.
 
 ROUTES.  kernel_ids() parses profiler kernel names (demangled or mangled) to ids such as gemm64_kernel<32,0,0,1,0,4,3>;
-routes() restates -- independently of _ext and of the C++ launcher -- which kernels a gemm_grouped call must reach: the
-Python choice of tile (pick_tile, GEMM_TILE_ROWS, TILE256_MIN_K, the row-map fallback, all_mid_ok) and the C++ choice of
-variant (long_k, the four-K-tile form, the _det kernels, the two stream-K forms) together.  Moving a threshold in either
-place means editing this file in the same commit.
+routes() restates -- independently of the product, which this file must not import -- which kernels a gemm_grouped call must
+reach: the Python choice of tile (bridgeqa_amd/gemm_route.py: pick_tile, GEMM_TILE_ROWS, TILE256_MIN_K, the row-map fallback,
+mid_ok) and the C++ choice of variant (csrc/gemm_common.h gemm_form() and streamk_fits(), the launchers' long_k and
+four-K-tile rules, the _det kernels) together.  Moving a threshold in gemm_route.py, or a form in gemm_form(), means editing
+this file in the same commit; tests/test_gemm_bound_cpu.py compares both with it without a device.
 """
 import math
 import re
@@ -349,7 +350,7 @@ def wgrad_rows_supported(Ni, Nj):
     return 1 <= ti <= 5 and tj in (1, 2, 4) and ti + tj <= 7 and not (ti == 5 and tj == 1)
 
 
-# ---- every instantiation launch_gemm, launch_gemm_mid, launch_det_variant and bq_wgrad_rows_bf16 can reach -----------------------
+# ---- every instantiation launch_gemm, launch_gemm_mid and bq_wgrad_rows_bf16 can reach (csrc/gemm_common.h gemm_form()) ------------
 def _route_table():
     t = []
     bf16_forms = [(0, (EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_ADD)), (1, (EPI_NONE, EPI_DGELU, EPI_ADD))]
@@ -373,11 +374,8 @@ def _route_table():
 
 
 ROUTE_TABLE = _route_table()
-# instantiations in the library that no permitted argument combination reaches, or that are out of this suite's scope
+# instantiations in the library that are out of this suite's scope (none is left that no permitted combination reaches)
 NOT_REACHED = {
-    "gemm256_kernel<0,0,0,1,0>": "launch_gemm refuses fp32 output on tile 256 for a K-contiguous Q (instantiated by launch_variant only)",
-    "gemm256_kernel<0,0,1,1,0>": "the same with a bias",
-    "gemm256_kernel<1,0,0,1,0>": "the same with a contraction-major P",
     "gemm256_kernel<0,0,4,0,0>": "EPI_BIAS_CE, the LM-head cross-entropy epilogue: not launched by this battery; held to its own bound by tests/test_lmhead_bound_gpu.py",
     "pwconv64_kernel / pwconv64s_kernel": "the SharedMLP convolution kernels: out of scope (tests/test_modules_gpu.py)",
 }

@@ -282,3 +282,67 @@ def test_route_table_lists_each_instantiation_once():
     assert sum(k.startswith("gemm128_kernel<") for k in R.ROUTE_TABLE) == 12
     assert sum(k.startswith("gemm256_kernel<") for k in R.ROUTE_TABLE) == 9
     assert sum(k.startswith("wgrad_rows_kernel<") for k in R.ROUTE_TABLE) == 12
+
+
+# ---- the product's two statements of the routing against this reference, without a device ---------------------------------------
+_GRID_NI = (8, 64, 248, 256, 264, 768, 3072)
+_GRID_NJ = (1, 100, 512, 513, 1023, 1024, 16400)
+_GRID_KC = (64, 127, 128, 768, 2240, 2304, 3072)
+_GRID_FLAGS = (0, P_XC, OUT_F32, P_XC | OUT_F32, DW)
+_GRID_EPIS = (EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, R.EPI_BIAS_CE, EPI_ADD)
+
+
+def _both_tiles(problems, flags, epi):
+    """(product, reference) tile class of one launch; problems: (Ni, Nj, Kc, colsum, map) tuples"""
+    from bridgeqa_amd import gemm_route
+    got = gemm_route.auto_tile([gemm_route.Shape(*p) for p in problems], flags, epi)
+    want = R.auto_tile([dict(Ni=p[0], Nj=p[1], Kc=p[2], colsum=p[3], map=p[4]) for p in problems], flags, epi)
+    return got, want
+
+
+def test_product_tile_policy_equals_the_reference_on_the_full_grid():
+    """bridgeqa_amd/gemm_route.auto_tile (what _ext.gemm_grouped launches on) against gemm_ref.auto_tile: every threshold of
+    both from both sides, all flag sets and epilogues, column sums and row maps on and off, groups of one and of two"""
+    import itertools
+    from bridgeqa_amd import gemm_route
+    assert "gemm_route" not in vars(R) and not hasattr(gemm_route, "torch")      # (the reference stays independent; the policy pure)
+    assert gemm_route.GEMM_TILE_ROWS == R.GEMM_TILE_ROWS and gemm_route.TILE256_MIN_K == [R.TILE256_MIN_K]
+    n, seen = 0, set()
+    for flags, epi, cs, mp in itertools.product(_GRID_FLAGS, _GRID_EPIS, (False, True), (False, True)):
+        for Ni, Nj, Kc in itertools.product(_GRID_NI, _GRID_NJ, _GRID_KC):
+            got, want = _both_tiles([(Ni, Nj, Kc, cs, mp)], flags, epi)
+            assert got == want, ((Ni, Nj, Kc, cs, mp), flags, epi, got, want)
+            seen.add(got)
+            n += 1
+    assert n == 7 * 7 * 7 * 5 * 6 * 4 and seen == {32, 64, 128, 256}
+    # groups of two from the corners of the grid; the second member carries the column sums / the row map
+    corners = list(itertools.product((_GRID_NI[0], _GRID_NI[-1]), (_GRID_NJ[0], _GRID_NJ[-1]), (_GRID_KC[0], _GRID_KC[-1])))
+    for flags, epi, cs, mp in itertools.product(_GRID_FLAGS, _GRID_EPIS, (False, True), (False, True)):
+        for a, b in itertools.product(corners, corners):
+            got, want = _both_tiles([a + (False, False), b + (cs, mp)], flags, epi)
+            assert got == want, (a, b, cs, mp, flags, epi, got, want)
+    # one tile class per launch: a member with a single K tile cannot take tile 128 and moves its partner to 256 with it
+    assert _both_tiles([(3072, 16400, 3072, False, False)], P_XC, EPI_NONE) == (128, 128)
+    assert _both_tiles([(3072, 16400, 3072, False, False), (3072, 16400, 64, False, False)], P_XC, EPI_NONE) == (256, 256)
+
+
+def test_built_library_holds_exactly_the_route_table():
+    """the GEMM kernels hipcc emitted (gemm*, splitk_fold_det, wgrad_rows*: what kernel_ids() parses) are ROUTE_TABLE plus the
+    GEMM ids of NOT_REACHED, no more and no fewer -- ties csrc/gemm_common.h gemm_form() to the reference table"""
+    from bridgeqa_amd import build
+    build.build()
+    res = build.kernel_resources()
+    if res is None:
+        pytest.skip("objects were not compiled by this checkout's build.py (prebuilt library)")
+    built = R.kernel_ids(res)
+    want = set(R.ROUTE_TABLE) | R.kernel_ids(R.NOT_REACHED)
+    assert built == want, {"not in the table": sorted(built - want), "not built": sorted(want - built)}
+
+
+@pytest.mark.parametrize("epi", [-1, 6, 99])
+def test_library_refuses_an_epilogue_outside_the_enum(epi):
+    """bq_gemm_bf16 checks the epilogue before it reads a descriptor (null here: nothing can be launched)"""
+    from bridgeqa_amd import _ext
+    assert _ext._lib.bq_gemm_bf16(None, 0, 0, epi, 64, None) == _ext._D["BQ_EINVAL"]
+    msg = _ext._lib.bq_last_error()
+    assert b"epilogue" in msg and str(epi).encode() in msg, msg
