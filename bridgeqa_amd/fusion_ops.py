@@ -1479,6 +1479,98 @@ class DecodeCache(object):
         return self
 
 
+class BeamState(object):
+    """What generation.beam_search keeps between two steps, as static device buffers beside a DecodeCache (csrc/beam.hip,
+    include/bqhip_beam.h): beam scores, the token table, the id buffer the next decoder step reads, done flags, the count of
+    samples not yet done and the finished-hypothesis heaps (tokens included).  Everything but `ids` lies in ONE allocation, so
+    host() is one copy.  step(logits) runs one whole iteration of the search on the device -- it reads cur_len from cache.pos
+    (already incremented for the step) and reorders cache.anc in place -- and allocates, synchronises and copies nothing."""
+
+    _LAYOUT = (("beam_score", torch.float32, "S"), ("tokens", torch.int32, "SL"), ("done", torch.int32, "B"),
+               ("not_done", torch.int32, "H"), ("src", torch.int32, "S"), ("cand", torch.int64, "SK"),
+               ("top_score", torch.float32, "BK"), ("top_index", torch.int32, "BK"), ("heap_len", torch.int32, "B"),
+               ("heap_adds", torch.int32, "B"), ("heap_seq", torch.int32, "Bn"), ("heap_hyplen", torch.int32, "Bn"),
+               ("heap_sum", torch.float32, "Bn"), ("heap_score", torch.float64, "Bn"), ("heap_worst", torch.float64, "B"),
+               ("heap_tokens", torch.int32, "BnL"))
+
+    def __init__(self, cache, prompt_ids, num_beams, max_length, eos_token_id, pad_token_id, min_length=0, length_penalty=1.0,
+                 early_stopping=False):
+        from . import _ext
+        S, nb = prompt_ids.shape[0], int(num_beams)
+        if prompt_ids.dim() != 2 or prompt_ids.shape[1] != 1 or S % nb or S != cache.S:
+            raise RuntimeError("BeamState: one-token prompts for the cache's %d slots are needed" % cache.S)
+        self.cache, self.B, self.nb, self.S, self.max_length = cache, S // nb, nb, S, int(max_length)
+        self.eos, self.pad, self.min_length = int(eos_token_id), int(pad_token_id), int(min_length)
+        self.length_penalty, self.early_stopping = length_penalty, bool(early_stopping)
+        dev = prompt_ids.device
+        self.shapes = {"S": (S,), "SL": (S, self.max_length), "B": (self.B,), "H": (_ext.BEAM_MAX_LEN + 2,), "SK": (S, 2 * nb),
+                       "BK": (self.B, 2 * nb), "Bn": (self.B, nb), "BnL": (self.B, nb, self.max_length)}
+        self.offsets, n = {}, 0
+        for name, dtype, shape in self._LAYOUT:
+            self.offsets[name] = n
+            n += -(-_numel(self.shapes[shape]) * torch.empty(0, dtype=dtype).element_size() // 16) * 16
+        self.arena = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.t = self._views(self.arena)
+        self.t["beam_score"].view(self.B, nb)[:, 1:] = -1e9
+        self.t["tokens"][:, 0] = prompt_ids[:, 0].to(torch.int32)
+        self.t["not_done"].fill_(self.B)
+        self.t["heap_worst"].fill_(1e9)
+        self.ids = prompt_ids.to(torch.int64).clone(memory_format=torch.contiguous_format)
+        # n ** length_penalty as Python computes it: the device never calls pow
+        self.lenpow = torch.tensor([1.0] + [float(k ** length_penalty) for k in range(1, self.max_length + 1)],
+                                   dtype=torch.float64).to(dev)
+        self._desc = self._desc_key = None
+
+    def _views(self, arena):
+        out = {}
+        for name, dtype, shape in self._LAYOUT:
+            shp = self.shapes[shape]
+            nbytes = _numel(shp) * torch.empty(0, dtype=dtype).element_size()
+            out[name] = arena[self.offsets[name]:self.offsets[name] + nbytes].view(dtype).view(shp)
+        return out
+
+    def __getattr__(self, name):
+        t = self.__dict__.get("t")
+        if t is not None and name in t:
+            return t[name]
+        raise AttributeError(name)
+
+    def step(self, logits):
+        from . import _ext
+        key = (logits.data_ptr(), logits.dtype, tuple(logits.shape), logits.stride())
+        if key != self._desc_key:
+            self._desc = _ext.beam_state_desc(logits, self.B, self.nb, self.max_length, self.eos, self.pad, self.min_length,
+                                              self.early_stopping, pos=self.cache.pos, lenpow=self.lenpow, anc=self.cache.anc,
+                                              ids=self.ids, **self.t)
+            self._desc_key, self._logits = key, logits
+        _ext.beam_step(self._desc, logits.device)
+
+    def host(self):
+        """{name: CPU tensor} of everything but ids, by ONE copy"""
+        return self._views(self.arena.cpu())
+
+    def hypotheses(self, host):
+        """the heaps of host() as generation.BeamHypotheses, entries in list order -> (hyps, done)"""
+        from .generation import BeamHypotheses
+        hyps = []
+        for b in range(self.B):
+            h = BeamHypotheses(self.nb, self.length_penalty, self.early_stopping)
+            n = int(host["heap_len"][b])
+            for i in sorted(range(n), key=lambda i: int(host["heap_seq"][b, i])):
+                h.beams.append((float(host["heap_score"][b, i]),
+                                host["heap_tokens"][b, i, :int(host["heap_hyplen"][b, i])].tolist()))
+            h.worst_score = float(host["heap_worst"][b])
+            hyps.append(h)
+        return hyps, [bool(d) for d in host["done"].tolist()]
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
+
+
 # ---- answer ranking on the shared K/V of the question (csrc/attn_rank.hip) -------------------------------------------------------
 # The reference re-scores k candidate answers per question against question states tiled k times (models/blip_vqa_3d.py:509-566)
 # and every decoder layer projects the tiled rows to K / V.  The K / V of a question do not depend on the candidate: here they

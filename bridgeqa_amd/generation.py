@@ -21,6 +21,10 @@ Device-side: one decoder call per step for all B x beams slots; the top-2k selec
 (which candidate becomes which next beam) and the cache gather are tensor ops; only the finished-hypothesis heaps -- a
 few Python floats and token lists per sample -- live on the host, fed by one small copy per step (the reference's scorer
 does the same walk with a `.item()` per candidate).
+
+beam_search_device (below; BQ_BEAM_DEVICE=1, default off) keeps all of that on the device for eligible decodes: the same
+algorithm, with the order among equal scores fixed by include/bqhip_beam.h where torch.topk leaves it open.  beam_search stays
+the definition and the default, and parity with the reference stays unpinned for both routes alike.
 """
 import torch
 
@@ -127,4 +131,57 @@ def beam_search(step_fn, reorder_fn, input_ids, num_beams, max_length, eos_token
         out[b, :len(h)] = torch.tensor(h, dtype=torch.long)
         if len(h) < max_length:
             out[b, len(h)] = eos_token_id
+    return out.to(dev), torch.tensor(best_scores, dtype=torch.float32, device=dev)
+
+
+@torch.no_grad()
+def beam_search_device(session, state, stop_lag=1):
+    """beam_search with the loop on the device: session.step_beams() is one whole iteration (decoder step, top 2 * num_beams,
+    open beams, finished-hypothesis heaps, done flags, reorder -- med.DecodeSession on an ops.BeamState, csrc/beam.hip; one
+    graph replay per token after the first).  The decisions are beam_search's; what differs is the rounding of the fp32
+    log-softmax and the order among EQUAL scores, which torch.topk leaves open and include/bqhip_beam.h fixes.  Parity with the
+    reference stays unpinned exactly as the module docstring says: this route restates the same published algorithm.
+
+    The host holds the loop, the stop check and the tail.  The stop check never waits for the step it has just launched: after
+    every step the device's count of samples not yet done goes to a pinned buffer behind an event, and the loop reads the count
+    of the step `stop_lag` steps back.  A done sample's beams are padding and its heap is closed, so steps that run after every
+    sample is done change nothing: stop_lag = 0 (wait for the step itself), 1 (default) or None (never look: run to max_length)
+    return the same result.  Then ONE copy brings the heaps and the open beams over, and the tail is beam_search's."""
+    B, num_beams, max_length = state.B, state.nb, state.max_length
+    dev = state.arena.device
+    pinned = torch.zeros(max_length + 2, dtype=torch.int32).pin_memory() if stop_lag is not None else None
+    events = {}
+    cur_len = 1
+    while True:
+        session.step_beams()                                       # the step of length cur_len writes not_done[1 + cur_len]
+        if stop_lag is not None:
+            pinned[cur_len:cur_len + 1].copy_(state.not_done[1 + cur_len:2 + cur_len], non_blocking=True)
+            events[cur_len] = torch.cuda.Event()
+            events[cur_len].record()
+        cur_len += 1
+        if cur_len >= max_length:
+            break
+        seen = None if stop_lag is None else events.get(cur_len - 1 - stop_lag)
+        if seen is not None:
+            seen.synchronize()
+            if int(pinned[cur_len - 1 - stop_lag]) == 0:
+                break
+    # ---- BeamSearchScorer.finalize, as in beam_search: open beams of unfinished samples join the heaps; best per sample
+    host = state.host()
+    hyps, done = state.hypotheses(host)
+    ids_host, sc_host = host["tokens"][:, :cur_len], host["beam_score"]
+    best, best_scores = [], []
+    for b in range(B):
+        if not done[b]:
+            for k in range(num_beams):
+                hyps[b].add(ids_host[b * num_beams + k].tolist(), float(sc_host[b * num_beams + k]))
+        score, hyp = sorted(hyps[b].beams, key=lambda x: x[0])[-1]
+        best.append(hyp)
+        best_scores.append(score)
+    sent_max = min(max(len(h) for h in best) + 1, max_length)
+    out = torch.full((B, sent_max), state.pad, dtype=torch.long)
+    for b, h in enumerate(best):
+        out[b, :len(h)] = torch.tensor(h, dtype=torch.long)
+        if len(h) < max_length:
+            out[b, len(h)] = state.eos
     return out.to(dev), torch.tensor(best_scores, dtype=torch.float32, device=dev)

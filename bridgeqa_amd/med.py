@@ -380,7 +380,12 @@ _DECODE_CACHE = [os.environ.get("BQ_DECODE_CACHE", "1") != "0"]
 # ... with the second step captured and replayed for the rest of the decode (3.7x against 1.45x for the eager cache route at the
 # reference's shape, profiles/generate_decode.md: the default since it won at both question lengths); BQ_DECODE_GRAPH=0: eager
 _DECODE_GRAPH = [os.environ.get("BQ_DECODE_GRAPH", "1") != "0"]
-_DECODE_STATS = {"sessions": 0, "captures": 0}   # decode sessions opened / steps captured so far (tests)
+_DECODE_STATS = {"sessions": 0, "captures": 0, "beam_decodes": 0, "beam_captures": 0, "beam_steps": 0}   # decode sessions opened /
+#                 steps captured so far; decodes on the device-beam route / whole-iteration graphs captured / whole iterations
+#                 run (eagerly or by replay) so far (tests)
+# generate's beam search on the device (ops.BeamState, csrc/beam.hip, DecodeSession.step_beams, generation.beam_search_device) when
+# the decode is eligible for it; BQ_BEAM_DEVICE=1 switches it on.  Off by default.
+_BEAM_DEVICE = [os.environ.get("BQ_BEAM_DEVICE", "0") == "1"]
 # rank_answer on the K/V of the UNTILED question states + the candidate attention kernels (ops.RankShared, csrc/attn_rank.hip)
 # whenever the call is eligible (BertLMHeadModel.rank_shared).  BQ_RANK_SHARED=1 turns it on; off by default: faster at six of the
 # eight sizes of the A/B table, 1-4 % slower at two (profiles/rank_answer.md, tools/bench_rank.py)
@@ -892,12 +897,49 @@ class DecodeSession(object):
     position, reorder(beam_idx) after the beams moved.  graph=True (generate's default, _DECODE_GRAPH): the first step runs
     eagerly (it also warms every kernel and operand cache up), the second is captured -- embeddings -> layers -> LM-head logits on ONE stream, no fork, reading
     the token ids from a static buffer and the position from the cache's device counter -- and replayed from then on; the
-    logits it returns are then a STATIC buffer the next step overwrites.  Top-k, beam bookkeeping and reorder stay outside."""
+    logits it returns are then a STATIC buffer the next step overwrites.  Driven through step / reorder, top-k, beam bookkeeping
+    and reorder stay outside (generation.beam_search).
+
+    With an ops.BeamState attached (attach_beams; generate's device_beams route, _BEAM_DEVICE) step_beams() is one whole
+    iteration of the search: decoder forward from the state's id buffer, the position increment, the beam kernels
+    (csrc/beam.hip: selection, finished-hypothesis heaps, the next ids) and the reorder of the ancestry table, on one stream
+    without a fork -- eager for the first step, ONE captured graph replayed for every further token when graph=True.  Nothing in
+    it reaches the host; the host mirror cache.t keeps counting.  A session is driven one way or the other, not both."""
 
     def __init__(self, model, cache, graph=False):
         self.model, self.cache, self.use_graph = model, cache, bool(graph)
-        self.graph = self.ids = self.logits = None
+        self.graph = self.ids = self.logits = self.beams = None
         _DECODE_STATS["sessions"] += 1
+
+    def attach_beams(self, state):
+        if self.cache.t != 0 or self.graph is not None or state.cache is not self.cache:
+            raise RuntimeError("DecodeSession.attach_beams: a fresh session and a BeamState on its cache are needed")
+        self.beams = state
+        return self
+
+    @torch.no_grad()
+    def step_beams(self):
+        c, st = self.cache, self.beams
+        if st is None:
+            raise RuntimeError("DecodeSession.step_beams: no BeamState attached")
+        if c.t >= c.Lmax:
+            raise RuntimeError("DecodeSession: the cache holds %d positions" % c.Lmax)
+        _DECODE_STATS["beam_steps"] += 1
+        if not self.use_graph or c.t == 0:
+            logits = self._forward(st.ids)
+            c.advance()
+            st.step(logits)
+            return
+        if self.graph is None:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.logits = self._forward(st.ids)
+                c.pos.add_(1)
+                st.step(self.logits)
+            _DECODE_STATS["captures"] += 1
+            _DECODE_STATS["beam_captures"] += 1
+        self.graph.replay()
+        c.t += 1
 
     def _forward(self, ids):
         out = self.model(input_ids=ids, past_key_values=self.cache, use_cache=True, is_decoder=True, return_dict=True)
@@ -1065,11 +1107,14 @@ class BertLMHeadModel(BertPreTrainedModel):
 
     @torch.no_grad()
     def generate(self, input_ids, max_length=20, min_length=0, num_beams=1, eos_token_id=None, pad_token_id=None,
-                 length_penalty=1.0, early_stopping=False, return_scores=False, graph=None, **model_kwargs):
+                 length_penalty=1.0, early_stopping=False, return_scores=False, graph=None, device_beams=None, **model_kwargs):
         """beam search as `transformers` v4.15 `generate` runs it for a decoder-only model (generation.py; parity
         unpinned): input_ids (B, L0) is repeated num_beams times per sample; encoder_hidden_states / encoder_attention_mask
-        must already have B * num_beams rows (the caller chooses what every beam slot attends to)."""
-        from .generation import beam_search
+        must already have B * num_beams rows (the caller chooses what every beam slot attends to).
+        device_beams (None: BQ_BEAM_DEVICE, off by default): keep the search itself on the device -- taken only when the decode
+        is eligible for the static cache AND 1 <= num_beams <= 16, vocabulary >= 2 num_beams + 1, 2 <= max_length <= 64 and
+        eos / pad are token ids; checked before the first step, anything else runs the host search below bit for bit."""
+        from .generation import beam_search, beam_search_device
         if eos_token_id is None or pad_token_id is None:
             raise ValueError("generate needs eos_token_id and pad_token_id")
         ids = input_ids.repeat_interleave(num_beams, dim=0)
@@ -1081,6 +1126,15 @@ class BertLMHeadModel(BertPreTrainedModel):
         # two closures after them do by growing and index_select-ing the reference's cache; graph: replay one captured step
         # (None: BQ_DECODE_GRAPH)
         session = self.decode_session(ids, max_length, enc, model_kwargs.get("encoder_attention_mask"), graph=graph)
+        use_device = _BEAM_DEVICE[0] if device_beams is None else bool(device_beams)
+        V = self.config.vocab_size
+        if session is not None and use_device and 1 <= num_beams <= 16 and V >= 2 * num_beams + 1 and 2 <= max_length <= 64 \
+                and 0 <= eos_token_id < V and 0 <= pad_token_id < V:
+            state = ops.BeamState(session.cache, ids, num_beams, max_length, eos_token_id, pad_token_id, min_length=min_length,
+                                  length_penalty=length_penalty, early_stopping=early_stopping)
+            _DECODE_STATS["beam_decodes"] += 1
+            seq, scores = beam_search_device(session.attach_beams(state), state)
+            return (seq, scores) if return_scores else seq
         if session is not None:
             seq, scores = beam_search(lambda cur, past: (session.step(cur[:, -1:]), session),
                                       lambda past, beam_idx: past.reorder(beam_idx), ids, num_beams, max_length,

@@ -13,6 +13,7 @@
 #include "bqhip_lstm.h" /* bq_lstm_fwd / bq_lstm_bwd: additive to ABI 6 */
 #include "bqhip_scene.h" /* bq_scene_boxes / bq_scene_sample / bq_scene_votes: additive to ABI 6 */
 #include "bqhip_view.h"  /* bq_view_prep: additive to ABI 6 */
+#include "bqhip_beam.h"  /* bqx_beam_step: additive to ABI 6 */
 
 #ifdef __cplusplus
 extern "C" {
