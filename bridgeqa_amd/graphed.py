@@ -30,7 +30,7 @@ ordinary eager path.
 Round 5 additions, all outside the loop BODY:
   * `prefetch_loader(model, dataloader)` around the loop's iterable (or `model._graphed.prefetch(next_point_clouds)`): the
     NEXT batch's sampling / grouping indices (FPS, ball query, three-NN: coordinates only, no parameters) run on the
-    detector stream under THIS step's fusion, as pipeline.PhasedTrainStep does; without an announcement a step computes its
+    detector stream under THIS step's fusion (step_phases.GeometryBuffers); without an announcement a step computes its
     own geometry in front of its detector forward, as before.
   * `wrap_optimizer(model, optimizer)`: `optimizer.step()` replays a captured graph of the fused update (and
     `optimizer.zero_grad()` launches nothing: the captured backward overwrites every gradient).
@@ -43,6 +43,7 @@ Round 5 additions, all outside the loop BODY:
 import torch
 
 from . import fusion_ops as ops
+from . import step_phases as phases
 
 
 _INPUT_KEYS = ("point_clouds", "images", "question", "answer")
@@ -251,7 +252,7 @@ def _rebuild(x, repl, path=()):
 class GraphedRunner(object):
     # what one capture owns (a change of input signature stashes the set and restores / captures another: `_cache`)
     _BUNDLE = ("graphs", "sig", "static_in", "diff", "static_grads", "_st", "static_param_grads", "out_keys", "losses", "_pools",
-               "anchor", "_geo_next", "_geo_cur", "next_xyz", "_geo_key", "_t_generation", "opt_graphs", "_static_ids")
+               "anchor", "_geo", "next_xyz", "_geo_key", "_t_generation", "opt_graphs", "_static_ids")
 
     def __init__(self, model, warmup=2, comm_dtype=torch.float32, process_group=None, max_cached=2):
         self.model, self.warmup = model, int(warmup)
@@ -265,10 +266,11 @@ class GraphedRunner(object):
         self.phase_events = None # set to {} to bracket every graph with events on its stream (phase_gpu_ms())
         # geometry prefetch (prefetch() / prefetch_loader): off until the first announcement
         self.prefetching = False
-        self._geo_next = self._geo_cur = self.next_xyz = None
-        self._geo_key = None        # which batch the indices in `_geo_next` belong to
+        self._geo = self.next_xyz = None   # (step_phases.GeometryBuffers of the current captured set)
+        self._geo_key = None        # which batch the indices in `_geo.next` belong to
         self._announced = None      # (point clouds, key) of the batch to compute under the NEXT forward's fusion
         self._t_generation = None
+        self._bn_modules = phases.batchnorm_modules(model)   # (taken again at every capture)
         self.opt_graphs = {}
         self._static_ids = frozenset()
         # signature -> stashed capture (LRU); `captures` counts them (a loader with varying token length re-captures on
@@ -301,9 +303,7 @@ class GraphedRunner(object):
             for kk, t in items:
                 if torch.is_tensor(t):
                     sig.append((k, kk, tuple(t.shape), t.dtype, str(t.device)))
-        bn = tuple(mod.momentum for mod in self.model.modules() if isinstance(mod, torch.nn.modules.batchnorm._BatchNorm))
-        # (the deterministic mode selects other kernels: graphs captured under one mode are never replayed under the other)
-        return tuple(sig) + (bn, ("deterministic", ops.is_deterministic()))
+        return tuple(sig) + (phases.replay_signature(self._bn_modules),)
 
     def _copy_inputs(self, data_dict):
         for k in _INPUT_KEYS:
@@ -315,7 +315,7 @@ class GraphedRunner(object):
             elif src.data_ptr() != dst.data_ptr():
                 dst.copy_(src, non_blocking=True)
 
-    # ---- the phases (each on one stream; the same cuts as pipeline.PhasedTrainStep) ----------------------------------
+    # ---- the phases (each on one stream; what they share with pipeline.PhasedTrainStep is step_phases') --------------
     def _inputs(self):
         dd = {k: (dict(v) if isinstance(v, dict) else v) for k, v in self.static_in.items()}
         dd["phase"] = "train"
@@ -326,51 +326,26 @@ class GraphedRunner(object):
         st["img"] = self.model.encode_image(self._inputs())
 
     def _t_refresh(self, st):
-        """the K-contiguous weight copies of this step's input-gradient GEMMs (fusion_state.transposed_shadow),
-        re-transposed from what the caller's optimizer.step() left: detector stream, behind the detector forward, beside the
-        fusion's forward chain (pipeline.PhasedTrainStep's t_refresh phase); the fusion backward waits for it"""
-        if ops.TRANSPOSED_DX[0] and not (torch.cuda.is_current_stream_capturing() and ops._T_STATE["dirty"]):
-            ops.refresh_transposed(self.dev)
+        """step_phases.t_refresh of what the caller's optimizer.step() left: detector stream, behind the detector forward,
+        beside the fusion's forward chain; the fusion backward waits for it"""
+        phases.t_refresh(self.dev)
 
     def _geometry(self, st):
-        """sampling / grouping indices of the point clouds in `next_xyz` into the persistent `_geo_next` set
-        (Pointnet2Backbone.precompute_geometry: FPS picks, centres, ball-query groups of the four SA levels, three-NN of
-        the two FP levels -- coordinates only)"""
-        from .pointnet2_utils import background_geometry
-        with background_geometry():   # (the gentle ball-query grid: this phase runs beside the fusion chain)
-            geo = self.model.detection_backbone.precompute_geometry(self.next_xyz)
-        if self._geo_next is None:
-            self._geo_next = {k: v.clone() for k, v in geo.items()}
-        else:
-            for k, v in geo.items():
-                self._geo_next[k].copy_(v)
+        """sampling / grouping indices of the point clouds in `next_xyz` into the persistent `_geo.next` set"""
+        self._geo.compute(self.model.detection_backbone, self.next_xyz)
 
     def _det_fwd(self, st):
         dd = self._inputs()
         # the token-only head of the fusion (question / answer embeddings, BLIP_VQA3D.prepare_text) rides on the detector
-        # stream, beside the image encoder; its backward opens the detector's backward phase (as pipeline.PhasedTrainStep's
-        # text_prep / text_prep_bwd phases)
+        # stream, beside the image encoder; its backward opens the detector's backward phase
         bm = self.model.blip_model
         st["prep"] = bm.prepare_text(dd["question"], dd.get("answer"), self.dev) if hasattr(bm, "prepare_text") else None
         if self.prefetching:
-            # next -> cur: this step's backward keeps reading `cur` while the prefetch under its fusion refills `next`
-            if self._geo_cur is None:
-                self._geo_cur = {k: v.clone() for k, v in self._geo_next.items()}
-            else:
-                for k, v in self._geo_next.items():
-                    self._geo_cur[k].copy_(v)
-            dd["geometry"] = self._geo_cur
+            dd["geometry"] = self._geo.rotate()
         st["dd"] = self.model.detect_objects(dd)
 
     def _fusion_fwd(self, st):
-        st["img_leaf"] = st["img"].detach().requires_grad_(True)
-        st["obj_leaf"] = st["dd"]["object_feat"].detach().requires_grad_(True)
-        dd = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in st["dd"].items()}
-        prep = None
-        if st.get("prep") is not None:
-            prep = dict(st["prep"])
-            st["prep_leaves"] = {k: prep[k].detach().requires_grad_(True) for k in ("q_embeds", "a_embeds") if k in prep}
-            prep.update(st["prep_leaves"])
+        dd, st["img_leaf"], st["obj_leaf"], prep, st["prep_leaves"] = phases.cut_for_fusion(st["img"], st["dd"], st["prep"])
         st["fd"] = self.model.fuse(dd, st["img_leaf"], st["obj_leaf"], text_prep=prep)
 
     def _diff_outputs(self, st):
@@ -387,27 +362,18 @@ class GraphedRunner(object):
 
     def _fusion_bwd(self, st):
         outs = [(t, g) for (k, t, ph), g in zip(self.diff, self.static_grads) if ph == "fusion"]
-        ops.begin_deferred_wgrad()
-        try:
+        with phases.deferred_wgrad():
             torch.autograd.backward([t for t, _ in outs], [g for _, g in outs])
-        finally:
-            ops.flush_deferred_wgrad()
         st["img_grad"], st["obj_grad"] = st["img_leaf"].grad, st["obj_leaf"].grad
 
     def _det_bwd(self, st):
-        if st.get("prep") is not None:
-            roots = [(st["prep"][k], leaf.grad) for k, leaf in st["prep_leaves"].items() if leaf.grad is not None]
-            if roots:
-                torch.autograd.backward([t for t, _ in roots], [g for _, g in roots])
+        phases.text_prologue_backward(st["prep"], st["prep_leaves"])
         outs = [(t, g) for (k, t, ph), g in zip(self.diff, self.static_grads) if ph == "det"]
         torch.autograd.backward([t for t, _ in outs] + [st["dd"]["object_feat"]], [g for _, g in outs] + [st["obj_grad"]])
 
     def _image_bwd(self, st):
-        ops.begin_deferred_wgrad()
-        try:
+        with phases.deferred_wgrad():
             st["img"].backward(st["img_grad"])
-        finally:
-            ops.flush_deferred_wgrad()
 
     # ---- scheduling ---------------------------------------------------------------------------------------------------
     def _forward_phases(self, run):
@@ -440,7 +406,7 @@ class GraphedRunner(object):
                 run("geometry")              # the NEXT batch's indices, under this step's fusion
                 self._geo_key = key
             elif self.prefetching:
-                self._geo_key = None         # `_geo_next` still holds this batch's indices: nothing announced
+                self._geo_key = None         # `_geo.next` still holds this batch's indices: nothing announced
         with torch.cuda.stream(self.s_main):
             self.s_main.wait_event(self.e_det_fwd)
             run("fusion_fwd")
@@ -505,38 +471,19 @@ class GraphedRunner(object):
         return run
 
     def _replay(self, name):
-        if self.host_times is None and self.phase_events is None:
-            self.graphs[name].replay()
-            return
-        import time
-        s_ = torch.cuda.current_stream(self.dev)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s_)
-        t0 = time.perf_counter()
-        self.graphs[name].replay()
-        if self.host_times is not None:
-            self.host_times.setdefault(name, []).append((time.perf_counter() - t0) * 1e3)
-        e1.record(s_)
-        if self.phase_events is not None:
-            self.phase_events.setdefault(name, []).append((e0, e1))
+        self._replay_named(name, self.graphs[name])
+
+    def _replay_named(self, name, g):
+        phases.timed_launch(name, g.replay, self.dev, self.host_times, self.phase_events)
 
     def phase_gpu_ms(self):
-        """after a synchronize: {graph: (mean start, mean end)} in ms from the start of the step's first graph"""
-        out = {}
-        steps = min(len(v) for v in self.phase_events.values())
-        ref = self.phase_events["image_fwd"][-steps:]
-        for name, evs in self.phase_events.items():
-            evs = evs[-steps:]     # (aligned at the END: a step that computed its own geometry has an extra, earlier entry)
-            a = [ref[i][0].elapsed_time(evs[i][0]) for i in range(steps)]
-            b = [ref[i][0].elapsed_time(evs[i][1]) for i in range(steps)]
-            out[name] = (sum(a) / steps, sum(b) / steps)
-        return out
+        """after a synchronize: {graph: (mean start, mean end)} in ms from the start of the step's first graph (a step that
+        computed its own geometry has an extra, earlier entry for it)"""
+        return phases.phase_gpu_ms(self.phase_events, "image_fwd")
 
     # ---- capture --------------------------------------------------------------------------------------------------------
     def capture(self, data_dict):
-        # single-stream graphs: a graph with an internal fork (fusion_ops.fork: the decoder's hoisted K/V projection on a
-        # side stream) is enqueued node by node by this runtime -- 8.8 ms of host time for the fusion forward, which then
-        # ran 12.2 ms on the GPU instead of ~4.5
+        # (the warm-up passes run as the phases are captured: single-stream, step_phases.capture_phases)
         prev = ops.set_overlap(False)
         announced, self._announced = self._announced, None   # (the warm-up passes must not consume the announcement)
         self._in_capture = True
@@ -549,11 +496,8 @@ class GraphedRunner(object):
 
     def _capture(self, data_dict):
         m = self.model
-        # an earlier eager forward can survive as a reference CYCLE (fusion_ops.HoistedKV <-> its autograd node): its
-        # AccumulateGrad nodes -- born on the caller's stream -- would be reused by the capture and hipStreamEndCapture faults
-        # on them; collect before capturing
-        import gc
-        gc.collect()
+        phases.collect_dead_autograd()
+        self._bn_modules = phases.batchnorm_modules(m)
         self.dev = dev = data_dict["point_clouds"].device
         self.static_in = {k: ({kk: (t.clone() if torch.is_tensor(t) else t) for kk, t in v.items()} if isinstance(v, dict)
                               else v.clone()) for k, v in ((k, data_dict[k]) for k in _INPUT_KEYS)}
@@ -564,7 +508,7 @@ class GraphedRunner(object):
             self._streams_ready = True
             self._setup_data_parallel(dev)
         self.anchor = torch.zeros(1, device=dev, requires_grad=True)
-        self._geo_next = self._geo_cur = None
+        self._geo = phases.GeometryBuffers()
         self._geo_key, self._geo_ready = None, False
         self.next_xyz = data_dict["point_clouds"][..., :3].contiguous().clone() if self.prefetching else None
         self.opt_graphs = {}
@@ -610,10 +554,9 @@ class GraphedRunner(object):
             for k, v in m.named_buffers():
                 v.copy_(saved_buf[k])
         if ops.TRANSPOSED_DX[0]:
-            ops.refresh_transposed(dev)   # (builds the device table of what the warm-up registered: not possible inside a capture)
-            self._t_generation = ops.transposed_generation()   # (its tables and operands live as long as these graphs)
-        # capture: one graph per phase, a pool per stream (the two streams' graphs run concurrently); the geometry and the
-        # weight-copy refresh in pools of their own (they replay out of capture order: before OR after the detector forward)
+            self._t_generation = phases.prepare_t_refresh(dev)
+        # capture: a pool per stream; the geometry and the weight-copy refresh in pools of their own (they replay out of
+        # capture order: before OR after the detector forward)
         pools = self._pools = {"main": torch.cuda.graph_pool_handle(), "det": torch.cuda.graph_pool_handle(),
                                "geo": torch.cuda.graph_pool_handle(), "aux": torch.cuda.graph_pool_handle()}
         self.losses = {}
@@ -621,20 +564,15 @@ class GraphedRunner(object):
             ("det_fwd", "det", "det"),) + ((("t_refresh", "det", "aux"),) if ops.TRANSPOSED_DX[0] else ()) + (
             ("fusion_fwd", "main", "main"),
             ("fusion_bwd", "main", "main"), ("image_bwd", "main", "main"), ("det_bwd", "det", "det"))
-        st, graphs = {}, {}
-        streams = {"main": self.s_main, "det": self.s_det}
-        for name, which, pool in order:
+        st = {}
+
+        def seed_buffers(name):   # (what the backward graphs are seeded through: known once the forward is captured)
             if name == "fusion_bwd":
                 self.diff = self._diff_outputs(st)
                 self.static_grads = [torch.zeros_like(t) for _, t, _ in self.diff]
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g, pool=pools[pool], stream=streams[which]):
-                    getattr(self, "_" + name)(st)
-            except Exception as e:
-                raise RuntimeError("graphed.enable: phase '%s' could not be captured: %s" % (name, e)) from e
-            graphs[name] = g
-            torch.cuda.synchronize(dev)
+        graphs = phases.capture_phases(order, lambda name: getattr(self, "_" + name)(st),
+                                       {"main": self.s_main, "det": self.s_det}, pools, "graphed.enable",
+                                       before_phase=seed_buffers)
         self._st = st                       # keeps the captured autograd graph and the static outputs alive
         self.graphs = graphs
         self.static_param_grads = [(p, p.grad) for p in params if p.grad is not None]
@@ -715,13 +653,12 @@ class GraphedRunner(object):
     # ---- the two calls ------------------------------------------------------------------------------------------------
     def forward(self, data_dict):
         self._switch(data_dict)
-        if not self._bwd_done:
-            pass   # (a forward without a backward -- e.g. a skipped step -- is fine: the next replay overwrites everything)
+        # (a forward without a backward -- e.g. a skipped step -- is fine: the next replay overwrites everything)
         self.step_id += 1
         self._bwd_done = False
         self._opt_pending = False
         if self.prefetching:
-            # do the indices in `_geo_next` belong to THIS batch?  prefetch_loader's string key, or the very tensor that
+            # do the indices in `_geo.next` belong to THIS batch?  prefetch_loader's string key, or the very tensor that
             # was announced (same object, not written since)
             pc = data_dict["point_clouds"]
             key = data_dict.get("_bq_geometry_key")
@@ -936,16 +873,6 @@ class GraphedRunner(object):
         # (no Python runs in a replay: the post-step hook that marks the K-contiguous weight copies stale did not fire)
         ops.mark_transposed_stale()
         return None
-
-    def _replay_named(self, name, g):
-        if self.host_times is None and self.phase_events is None:
-            g.replay()
-            return
-        saved, self.graphs = self.graphs, dict(self.graphs, **{name: g})
-        try:
-            self._replay(name)
-        finally:
-            self.graphs = saved
 
     # ---- geometry prefetch ------------------------------------------------------------------------------------------------
     def prefetch(self, next_point_clouds, key=None):

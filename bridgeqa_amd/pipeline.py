@@ -35,9 +35,10 @@ back to back in launch order whatever the priorities -- CU masking would fix tha
 away from the encoder for the whole step.  The schedule therefore puts the detector's parameter-free work where it
 overlaps and accepts the rest.
 
-Autograd is cut at the two tensors that cross streams (image_embeds, object_feat): the fusion phase differentiates
-w.r.t. detached leaves and the branch backward phases are seeded with those leaf gradients -- the same gradients as
-one backward over the whole graph (chain rule), asserted in tests/test_pipeline_*.
+Autograd is cut at the tensors that cross streams (image_embeds, object_feat, the text prologue's embeddings): the fusion
+phase differentiates w.r.t. detached leaves and the branch backward phases are seeded with those leaf gradients
+(step_phases.cut_for_fusion).  What a phase shares with graphed.GraphedRunner, and the rules of capturing one, are stated in
+step_phases; the phase list, the streams and the schedule below are this step's own.
 
 Reference: the work of one iteration of scripts/train.py -> lib/solver.py:_forward/_backward (models/qa_module.py
 forward) restricted to the hot path; the optimizer is the caller's.
@@ -45,9 +46,9 @@ forward) restricted to the hot path; the optimizer is the caller's.
 import torch
 
 from . import fusion_ops as ops
+from . import step_phases as phases
 
 
-_DET_LOSS_LATE = [True]   # the fusion waits for the detector's outputs only (False: also for its loss, as before round 3)
 _T_REFRESH_WGS = [0]      # workgroups of the t_refresh launch (0: one per 64 x 64 tile, ~66 000; 256 / 96 walking the tiles measured 0.1-0.3 % slower)
 _DET_PRIORITY = [0]       # default stream priority of the detector stream (the main stream: -1, higher)
 _SINGLE_STREAM = [True]   # capture every phase graph without fusion_ops.fork (tools/ab_bench.py flips it)
@@ -96,9 +97,6 @@ class PhasedTrainStep(object):
         self.next_batch = next_batch if next_batch is not None else batch
         self.prefetch = (next_batch is not None) if prefetch_geometry is None else bool(prefetch_geometry)
         self.eager_phases = tuple(eager_phases)
-        # weight / bias gradients of every linear are parked during a backward phase and produced by ONE grouped GEMM
-        # launch per tile class + one grouped column-sum launch at its end (fusion_ops.begin/flush_deferred_wgrad)
-        self.defer_wgrad = True
         self.image_splits = max(1, int(image_bwd_splits))
         vit = model.blip_model.visual_encoder
         depth = len(vit.blocks)
@@ -115,11 +113,10 @@ class PhasedTrainStep(object):
         self.buffer_broadcaster, self.coverage_every, self._steps = buffer_broadcaster, int(coverage_every), 0
         self.reducers = dict(reducers or {})
         self.s_comm = torch.cuda.Stream(device=batch["point_clouds"].device) if self.reducers else None
-        self.e_img_bwd = torch.cuda.Event()
         self.e_img_seg = [torch.cuda.Event() for _ in range(self.image_splits)]
         self._comm_events = []
         self.comm_stall = None   # set to [] to time how long the main stream waits for the gradient exchanges (exposed time)
-        self._geo_next, self._geo_cur = None, None
+        self._geo = phases.GeometryBuffers()
         self.host_times = None  # set to {} to record the host time of every graph launch (ms, per phase)
         self.phase_events = None  # set to {} to bracket every phase with events on its stream (phase_gpu_ms())
         dev = batch["point_clouds"].device
@@ -130,8 +127,6 @@ class PhasedTrainStep(object):
         # (the process-wide pair: fusion_state.phase_streams -- a second runner must not open more streams)
         self.s_main, self.s_det = ops.phase_streams(dev, int(main_priority),
                                                     int(_DET_PRIORITY[0] if det_priority is None else det_priority))
-        self.s_img = self.s_main
-        self.e_img_fwd = torch.cuda.Event()
         self.e_text_bwd, self.e_t_refresh = torch.cuda.Event(), torch.cuda.Event()
         self.t_refresh = bool(ops.TRANSPOSED_DX[0]) and bm is not None
         self.e_det_fwd, self.e_fused, self.e_det_bwd, self.e_done = (torch.cuda.Event() for _ in range(4))
@@ -155,25 +150,12 @@ class PhasedTrainStep(object):
 
     def _geometry(self):
         """sampling / grouping indices of the next batch, into the persistent `next` buffers"""
-        from .pointnet2_utils import background_geometry
-        with background_geometry():   # (the gentle ball-query grid: this phase runs beside the fusion chain)
-            geo = self.model.detection_backbone.precompute_geometry(self.next_batch["point_clouds"])
-        if self._geo_next is None:
-            self._geo_next = {k: v.clone() for k, v in geo.items()}
-        else:
-            for k, v in geo.items():
-                self._geo_next[k].copy_(v)
+        self._geo.compute(self.model.detection_backbone, self.next_batch["point_clouds"])
 
     def _det_fwd(self):
         dd = dict(self.batch)
         if self.prefetch:
-            # next -> cur: the backward of this step keeps reading `cur` while the prefetch refills `next`
-            if self._geo_cur is None:
-                self._geo_cur = {k: v.clone() for k, v in self._geo_next.items()}
-            else:
-                for k, v in self._geo_next.items():
-                    self._geo_cur[k].copy_(v)
-            dd["geometry"] = self._geo_cur
+            dd["geometry"] = self._geo.rotate()
         dd = self.model.detect_objects(dd)
         self._state["dd"] = dd
 
@@ -184,26 +166,14 @@ class PhasedTrainStep(object):
         self._state["prep"] = bm.prepare_text(self.batch["question"], self.batch.get("answer"), self.dev)
 
     def _t_refresh(self):
-        """the K-contiguous copies of the text side's weights that this step's small input-gradient GEMMs read
-        (fusion_state.transposed_shadow): ONE launch re-transposes all of them from the operands the previous step's
-        optimizer left.  Detector stream, after the detection loss: it runs beside the fusion's FORWARD chain, the
-        fusion's backward waits for it (at the head of the step it cost the image encoder 0.3 ms; left to the first use
+        """step_phases.t_refresh on the detector stream, after the detection loss: it runs beside the fusion's FORWARD chain,
+        the fusion's backward waits for it (at the head of the step it cost the image encoder 0.3 ms; left to the first use
         it would sit on the critical chain)."""
-        if not (torch.cuda.is_current_stream_capturing() and ops._T_STATE["dirty"]):
-            ops.refresh_transposed(self.dev, max_wgs=_T_REFRESH_WGS[0])
+        phases.t_refresh(self.dev, max_wgs=_T_REFRESH_WGS[0])
 
     def _text_prep_bwd(self):
-        """its backward (LayerNorm + embedding tables; the decoder's table is tied to the LM head: this adds to the gradient
-        the fusion phase left there): detector stream, after the fusion, beside the image backward"""
-        st = self._state
-        roots, seeds = [], []
-        for k in ("q_embeds", "a_embeds"):
-            leaf = st["prep_leaves"].get(k)
-            if leaf is not None and leaf.grad is not None:
-                roots.append(st["prep"][k])
-                seeds.append(leaf.grad)
-        if roots:
-            torch.autograd.backward(roots, seeds)
+        """its backward: detector stream, after the fusion, beside the image backward"""
+        phases.text_prologue_backward(self._state["prep"], self._state["prep_leaves"])
 
     def _det_loss(self):
         """the detection loss (~200 short launches, 1 ms) as a phase of its own: the fusion waits for the detector's OUTPUTS
@@ -212,15 +182,9 @@ class PhasedTrainStep(object):
 
     def _fusion(self):
         st = self._state
-        img_leaf = st["img"].detach().requires_grad_(True)
-        obj_leaf = st["dd"]["object_feat"].detach().requires_grad_(True)
-        dd = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in st["dd"].items()}
-        prep = None
-        if self.text_prologue:
-            # the embeddings computed by the text_prep phase enter as leaves; text_prep_bwd continues from their gradients
-            prep = dict(st["prep"])
-            st["prep_leaves"] = {k: prep[k].detach().requires_grad_(True) for k in ("q_embeds", "a_embeds") if k in prep}
-            prep.update(st["prep_leaves"])
+        # (the embeddings computed by the text_prep phase enter as leaves; text_prep_bwd continues from their gradients)
+        dd, img_leaf, obj_leaf, prep, st["prep_leaves"] = phases.cut_for_fusion(
+            st["img"], st["dd"], st["prep"] if self.text_prologue else None)
         dd = self.model.fuse(dd, img_leaf, obj_leaf, text_prep=prep)
         st["fusion_loss_t"] = self.fusion_loss(dd)
         st["fusion_leaves"] = (img_leaf, obj_leaf)
@@ -231,12 +195,8 @@ class PhasedTrainStep(object):
         st = self._state
         loss = st.pop("fusion_loss_t")
         img_leaf, obj_leaf = st.pop("fusion_leaves")
-        if self.defer_wgrad:
-            ops.begin_deferred_wgrad()  # dW / db of the linears: parked, then one grouped launch after the chain
-        try:
+        with phases.deferred_wgrad():
             loss.backward()
-        finally:
-            ops.flush_deferred_wgrad()
         st["img_grad"], st["obj_grad"] = img_leaf.grad, obj_leaf.grad
         st["fusion_loss"] = loss.detach()
 
@@ -244,16 +204,12 @@ class PhasedTrainStep(object):
         """block range `seg` of the image encoder's backward (0 = the last blocks; one range without splits)"""
         st = self._state
         cuts = st["img_cuts"]
-        if self.defer_wgrad:
-            ops.begin_deferred_wgrad()  # 48 ViT weight gradients -> one grouped launch of 1296 full-contraction tiles
-        try:
+        with phases.deferred_wgrad():   # 48 ViT weight gradients -> one grouped launch of 1296 full-contraction tiles
             if seg == 0:
                 st["img"].backward(st["img_grad"])
             else:
                 (x, n), (xl, nl) = cuts[len(cuts) - seg]
                 torch.autograd.backward([x, n], [xl.grad, nl.grad])
-        finally:
-            ops.flush_deferred_wgrad()
         if seg == self.image_splits - 1 and not torch.cuda.is_current_stream_capturing():
             st["img_cuts"] = []   # (eager steps: the cut activations die with the step; captured ones live in the pool)
         if self._seg_probe is not None:   # (dry eager step of attach_reducers)
@@ -286,15 +242,11 @@ class PhasedTrainStep(object):
         st = self._state
         self.loss = st["det_loss"].detach() + st["fusion_loss"]
 
-    # (phase, stream, memory pool): the image phases may sit on their own (CU-masked) stream but still alternate
-    # strictly with the main stream's phases, so they share its pool
+    # (phase, stream, memory pool) in capture order: every stream's phases always replay in this order
     _ORDER = (("text_prep", "det", "det"), ("det_fwd", "det", "det"), ("det_loss", "det", "det"), ("t_refresh", "det", "det"),
-              ("geometry", "det", "det"), ("image_fwd", "img", "main"),
-              ("fusion", "main", "main"), ("fusion_bwd", "main", "main"), ("text_prep_bwd", "det", "det"), ("det_bwd", "det", "det"), ("image_bwd", "img", "main"), ("image_bwd_1", "img", "main"),
-              ("image_bwd_2", "img", "main"), ("image_bwd_3", "img", "main"), ("finish", "main", "main"))
-
-    def _stream(self, which):
-        return {"main": self.s_main, "det": self.s_det, "img": self.s_img}[which]
+              ("geometry", "det", "det"), ("image_fwd", "main", "main"),
+              ("fusion", "main", "main"), ("fusion_bwd", "main", "main"), ("text_prep_bwd", "det", "det"), ("det_bwd", "det", "det"), ("image_bwd", "main", "main"), ("image_bwd_1", "main", "main"),
+              ("image_bwd_2", "main", "main"), ("image_bwd_3", "main", "main"), ("finish", "main", "main"))
 
     def _skipped(self, name):
         if name.startswith("image_bwd_"):
@@ -306,37 +258,16 @@ class PhasedTrainStep(object):
         return name == "geometry" and not self.prefetch
 
     def phase_gpu_ms(self):
-        """after a synchronize: {phase: (mean start, mean end)} in ms relative to the start of the step's first phase,
-        from the events recorded while phase_events was a dict"""
-        out = {}
-        steps = min(len(v) for v in self.phase_events.values())
-        for name, evs in self.phase_events.items():
-            a = [self.phase_events["det_fwd"][i][0].elapsed_time(evs[i][0]) for i in range(steps)]
-            b = [self.phase_events["det_fwd"][i][0].elapsed_time(evs[i][1]) for i in range(steps)]
-            out[name] = (sum(a) / steps, sum(b) / steps)
-        return out
+        """after a synchronize: {phase: (mean start, mean end)} in ms relative to the start of the detector forward, from
+        the events recorded while phase_events was a dict"""
+        return phases.phase_gpu_ms(self.phase_events, "det_fwd")
 
     def _run(self, name, eager):
-        if self.phase_events is not None:
-            s_ = torch.cuda.current_stream(self.dev)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s_)
-            self._run_inner(name, eager)
-            e1.record(s_)
-            self.phase_events.setdefault(name, []).append((e0, e1))
-        else:
-            self._run_inner(name, eager)
-
-    def _run_inner(self, name, eager):
+        """phase_events brackets every phase, host_times only the graph launches"""
         if eager or name in self.eager_phases:
-            getattr(self, "_" + name)()
-        elif self.host_times is not None:
-            import time
-            t0 = time.perf_counter()
-            self.graphs[name].replay()
-            self.host_times.setdefault(name, []).append((time.perf_counter() - t0) * 1e3)
+            phases.timed_launch(name, getattr(self, "_" + name), self.dev, None, self.phase_events)
         else:
-            self.graphs[name].replay()
+            phases.timed_launch(name, self.graphs[name].replay, self.dev, self.host_times, self.phase_events)
 
     def _reduce(self, group, after_event):
         """exchange one gradient group on the communication stream once `after_event` (its backward) has passed"""
@@ -356,7 +287,7 @@ class PhasedTrainStep(object):
         Host ORDER matters: a graph launch blocks the host while its stream's hardware queue is full, so at every
         point the detector stream's launches (short, its queue is usually empty) are issued before the main
         stream's -- otherwise the detector only gets its packets once the main stream has drained (measured)."""
-        sm, sd, si = self.s_main, self.s_det, self.s_img
+        sm, sd = self.s_main, self.s_det
         # whatever the caller enqueued on ITS stream before this step -- solver.BatchStager.advance() copies the next
         # batch into the static buffers there -- happens before any phase reads the batch
         cur = torch.cuda.current_stream(self.dev)
@@ -365,7 +296,7 @@ class PhasedTrainStep(object):
             # detector forward has written its BatchNorm statistics: e_done), on the caller's stream
             cur.wait_event(self.e_done)
             self.buffer_broadcaster.broadcast()
-        for s_ in {sm, sd, si}:
+        for s_ in (sm, sd):
             if s_ is not cur:
                 s_.wait_stream(cur)
         sd.wait_event(self.e_done)  # parameters of the previous step's optimizer
@@ -373,23 +304,15 @@ class PhasedTrainStep(object):
             if self.text_prologue:
                 self._run("text_prep", eager)
             self._run("det_fwd", eager)
-            if _DET_LOSS_LATE[0]:
-                self.e_det_fwd.record(sd)
+            self.e_det_fwd.record(sd)   # (the fusion waits for the detector's outputs only, not for its loss)
             self._run("det_loss", eager)
-            if not _DET_LOSS_LATE[0]:
-                self.e_det_fwd.record(sd)
             if self.t_refresh:
                 self._run("t_refresh", eager)
                 self.e_t_refresh.record(sd)
             if self.prefetch:
                 self._run("geometry", eager)
-        if si is not sm:
-            si.wait_event(self.e_done)
-        with torch.cuda.stream(si):
-            self._run("image_fwd", eager)
-            self.e_img_fwd.record(si)
         with torch.cuda.stream(sm):
-            sm.wait_event(self.e_img_fwd)
+            self._run("image_fwd", eager)
             sm.wait_event(self.e_det_fwd)
             self._run("fusion", eager)
             if self.t_refresh:
@@ -407,17 +330,13 @@ class PhasedTrainStep(object):
             self.s_comm.wait_event(self.e_text_bwd)
         self._reduce("fusion", self.e_fused)
         self._reduce("det", self.e_det_bwd)
-        si.wait_event(self.e_fused)
         for seg in range(self.image_splits):
-            with torch.cuda.stream(si):
+            with torch.cuda.stream(sm):
                 self._run("image_bwd" if seg == 0 else "image_bwd_%d" % seg, eager)
-                self.e_img_seg[seg].record(si)
+                self.e_img_seg[seg].record(sm)
             # (one range: the group is called "image"; several: "image_0" travels under the ranges that follow it)
             self._reduce("image" if self.image_splits == 1 else "image_%d" % seg, self.e_img_seg[seg])
-        with torch.cuda.stream(si):
-            self.e_img_bwd.record(si)
         with torch.cuda.stream(sm):
-            sm.wait_event(self.e_img_bwd)
             sm.wait_event(self.e_det_bwd)
             if self.comm_stall is not None and self._comm_events:
                 # exposed communication = how long the critical path stands at this point for the exchanges alone
@@ -444,10 +363,10 @@ class PhasedTrainStep(object):
         (Parameters that get no gradient on this path -- unused BLIP heads -- are left out, as DDP's
         find_unused_parameters would discover every step.)"""
         cur = torch.cuda.current_stream(self.dev)
-        for s_ in (self.s_main, self.s_det, self.s_img):
+        for s_ in (self.s_main, self.s_det):
             s_.wait_stream(cur)
         self.e_done.record(self.s_main)
-        if self.prefetch and self._geo_next is None:
+        if self.prefetch and self._geo.next is None:
             with torch.cuda.stream(self.s_det):
                 self._geometry()
         opt, self.opt = self.opt, None  # a dry step: no parameter update (replicas must not diverge)
@@ -493,27 +412,21 @@ class PhasedTrainStep(object):
                         "stream's wait for all groups in front of the optimizer phase"}
 
     def _bn_momenta(self):
-        """BatchNorm momentum is a HOST scalar baked into the captured launches (F.batch_norm and the bq BN kernels take
-        it by value): the reference's BNMomentumScheduler (lib/pointnet2/pytorch_utils.py BNMomentumScheduler, stepped
-        once per epoch) would have no effect under replay, so step() compares this signature and re-captures"""
+        """step_phases.replay_signature: step() compares it and re-captures"""
         if self._bn_modules is None:
-            self._bn_modules = [m for m in self.model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
-        # (so is the deterministic mode, which selects other kernels: a change of mode captures again as well)
-        return tuple(m.momentum for m in self._bn_modules) + (("deterministic", ops.is_deterministic()),)
+            self._bn_modules = phases.batchnorm_modules(self.model)
+        return phases.replay_signature(self._bn_modules)
 
     def capture(self, warmup=3, keep_warmup_updates=False, _again=False):
         """`warmup` eager steps on the phase streams (autograd's AccumulateGrad nodes remember the stream they were
-        created on -- they must be born on the stream that is later captured), then one graph per phase.  Graphs of
-        one stream share a memory pool (they always replay in capture order); the two streams' pools are separate
-        because their graphs run concurrently.  The warm-up steps are real optimizer steps on the first batch (the
-        optimizer state must exist before the capture); unless keep_warmup_updates, parameters, buffers (BatchNorm
+        created on -- they must be born on the stream that is later captured), then one graph per phase
+        (step_phases.capture_phases; a memory pool per stream).  The warm-up steps are real optimizer steps on the first
+        batch (the optimizer state must exist before the capture); unless keep_warmup_updates, parameters, buffers (BatchNorm
         running statistics), moments and the step count are put back afterwards, so training starts from the state
         the caller handed over."""
-        import gc
-        gc.collect()   # (dead autograd graphs of earlier eager forwards -- reference cycles -- must not lend their
-        #                AccumulateGrad nodes, born on another stream, to the capture: hipStreamEndCapture faults on them)
+        phases.collect_dead_autograd()
         cur = torch.cuda.current_stream(self.dev)
-        for s_ in (self.s_main, self.s_det, self.s_img):
+        for s_ in (self.s_main, self.s_det):
             s_.wait_stream(cur)
         self.e_done.record(self.s_main)
         if self.prefetch and not _again:  # (a re-capture keeps the geometry the previous step prefetched)
@@ -558,32 +471,13 @@ class PhasedTrainStep(object):
         self.zero_grad()
         self._state = {}
         if self.t_refresh:
-            ops.refresh_transposed(self.dev)   # (builds the device table of what the warm-up registered: not possible inside a capture)
-            # the captured t_refresh launch reads this generation's tables: they (and the operands they point at) live as
-            # long as these graphs do
-            self._t_generation = ops.transposed_generation()
+            self._t_generation = phases.prepare_t_refresh(self.dev)
         pools = {"main": torch.cuda.graph_pool_handle(), "det": torch.cuda.graph_pool_handle()}
-        # every phase graph SINGLE-STREAM (no fusion_ops.fork inside: the decoder's hoisted K/V projection stays on the
-        # chain's stream): this runtime enqueues a graph with an internal fork node by node -- the fusion graph's launch held
-        # the host for 35-38 ms and the phase ran 14.2 ms; without the fork 2.2 ms of host time and 12.7-13.4 ms (round 4,
-        # A/B/A on one box: 39.5 / 40.7 / 38.6 ms per step)
-        prev_overlap = ops.set_overlap(not _SINGLE_STREAM[0])
-        self.graphs = {}
         self._bn_sig = self._bn_momenta()
-        try:
-            for name, which, pool in self._ORDER:
-                if self._skipped(name) or name in self.eager_phases:
-                    continue
-                g = torch.cuda.CUDAGraph()
-                try:
-                    with torch.cuda.graph(g, pool=pools[pool], stream=self._stream(which)):
-                        getattr(self, "_" + name)()
-                except Exception as e:
-                    raise RuntimeError("PhasedTrainStep.capture: phase '%s' could not be captured: %s" % (name, e)) from e
-                self.graphs[name] = g
-                torch.cuda.synchronize(self.dev)
-        finally:
-            ops.set_overlap(prev_overlap)
+        order = [o for o in self._ORDER if not (self._skipped(o[0]) or o[0] in self.eager_phases)]
+        self.graphs = phases.capture_phases(order, lambda name: getattr(self, "_" + name)(),
+                                            {"main": self.s_main, "det": self.s_det}, pools, "PhasedTrainStep.capture",
+                                            single_stream=_SINGLE_STREAM[0])
         self.e_done.record(self.s_main)
         if self.reducers:
             from .ddp import check_coverage
