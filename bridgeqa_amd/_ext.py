@@ -2021,6 +2021,8 @@ def mlp_eval(layers, tail=None, grouped=None, rows=None, pool=False):
             out = torch.empty(R // d.S, n, dtype=torch.bfloat16, device=dev)
         else:
             out = torch.empty(R, n, dtype=torch.bfloat16, device=dev)
+        if R == 0:   # nothing to launch (and an empty tensor has no address to pass)
+            return out
         d.out, d.pool = out.data_ptr(), int(bool(pool))
         _check(_lib.bq_mlp_eval(ctypes.byref(d), _stream()), "mlp_eval")
     return out
