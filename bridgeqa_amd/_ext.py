@@ -1311,6 +1311,7 @@ GEMM_P_XC, GEMM_Q_XC, GEMM_OUT_F32, GEMM_BACKGROUND = (_D["BQ_GEMM_" + n] for n 
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_CE, EPI_ADD = (
     _D["BQ_GEMM_EPI_" + n] for n in ("NONE", "BIAS", "BIAS_GELU", "DGELU", "BIAS_CE", "ADD"))
 GEMM_DET = _D["BQ_GEMM_DET"]   # set by gemm_grouped itself in the deterministic mode
+GEMM_SECOND = _D["BQ_GEMM_SECOND"]   # set by gemm_grouped itself when a problem carries P2 / Q2
 _GemmDesc = _cabi.STRUCTS["bq_gemm_desc"]
 
 
@@ -1348,6 +1349,8 @@ def gemm_grouped(problems, flags, epilogue=EPI_NONE, tile=None, fixed_order=Fals
     """One launch for a list of problems out[j][i] = epilogue(sum_kc P(i,kc) Q(j,kc)) (include/bqhip_fusion.h,
     bq_gemm_bf16).  problems: dicts with P, Q, out (2-D tensors, contiguous last dim) and optional bias (fp32 (Ni,)),
     out2, aux, colsum (fp32 (Ni,), accumulated).  P: (Ni, Kc), or (Kc, Ni) with GEMM_P_XC; Q likewise over j.
+    P2 / Q2 (weight-gradient form on tile 256 only): a second row source, out = Q^T P + Q2^T P2 in the same launch (BQ_GEMM_SECOND;
+    Q2 may be a batched-row view of any rows per batch); such a problem takes two of the launch's bq_gemm_max_problems() entries.
     fixed_order: take the deterministic mode's form (a cut contraction summed in piece order instead of with fp32 atomics)
     for this launch whatever the mode -- for results that feed further backward passes."""
     if _det() or fixed_order:
@@ -1396,10 +1399,36 @@ def _gemm_pack(d, pr, flags, epilogue):
     return gemm_route.Shape(Ni, Nj, d.Kc, colsum is not None, bool(q_rpb or o_rpb))
 
 
+def _gemm_pack_second(d, pr, prim):
+    """the second row source of a weight gradient (problem keys P2 / Q2: dW = Q^T P + Q2^T P2 in one pass, BQ_GEMM_SECOND) as
+    the array entry behind its primary `prim`: no out.  The library checks the form, the tile and the extents."""
+    if pr.get("P2") is None or pr.get("Q2") is None:
+        raise RuntimeError("gemm: a second row source needs both P2 and Q2")
+    P2, Q2 = _mat(pr["P2"], "P2"), pr["Q2"]
+    qshape, ldq, q_rpb, q_bs = _mat_rows(Q2, "Q2")
+    if P2.dtype != torch.bfloat16 or Q2.dtype != torch.bfloat16:
+        raise RuntimeError("gemm: operands must be bf16")
+    if P2.shape[0] != qshape[0] or P2.shape[1] != prim.Ni or qshape[1] != prim.Nj:
+        raise RuntimeError("gemm: shape mismatch P2%s Q2%s for a (%d, %d) weight gradient" % (
+            tuple(P2.shape), tuple(Q2.shape), prim.Nj, prim.Ni))
+    d.P, d.Q = P2.data_ptr(), Q2.data_ptr()
+    d.ldp, d.ldq, d.q_rpb, d.q_bstride = P2.stride(0), ldq, q_rpb, q_bs
+    d.Ni, d.Nj, d.Kc, d.ksplit = prim.Ni, prim.Nj, P2.shape[0], 1
+
+
 def _gemm_grouped_launch(problems, flags, epilogue, tile):
-    n = len(problems)
+    two = [("P2" in pr) or ("Q2" in pr) for pr in problems]
+    n = len(problems) + sum(two)
     arr = (_GemmDesc * n)()
-    shapes = [_gemm_pack(arr[k], pr, flags, epilogue) for k, pr in enumerate(problems)]
+    shapes, k = [], 0
+    for pr, second in zip(problems, two):
+        shapes.append(_gemm_pack(arr[k], pr, flags, epilogue))
+        k += 1
+        if second:
+            _gemm_pack_second(arr[k], pr, arr[k - 1])
+            k += 1
+    if any(two):
+        flags |= GEMM_SECOND
     tile = int(tile or gemm_route.auto_tile(shapes, flags, epilogue))
     dev = problems[0]["out"].device
     if tile != 128:

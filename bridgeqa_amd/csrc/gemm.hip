@@ -98,11 +98,25 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs args) {
   const int i0 = bi * 256, j0 = bj * 256;
   const int Ni = pr.Ni, Nj = pr.Nj, Kc = pr.Kc;
   const int ldp = pr.ldp, ldq = pr.ldq;
-  const int nkt = SK ? kseg : (Kc + 63) >> 6;
+  // weight-gradient form only: a SECOND contraction segment (dW = Qa^T Pa + Qb^T Pb) in the next table entry.  Its K tiles
+  // follow segment a's in the same K loop, into the same accumulators and column-sum MFMAs; each segment is padded to whole K
+  // tiles by its own descriptor bounds (rows past a segment's end arrive as zeros), so no K tile holds rows of both.
+  constexpr bool SEG = P_XC && Q_XC && OUT_F32 && !SK;
+  bool has_b = false;
+  if constexpr (SEG) has_b = pr.has_seg() != 0;
+  const GemmProblem &sg = args.p[SEG && has_b ? pi + 1 : pi];
+  int nkt_a = 0, nkt_b = 0;
+  if constexpr (SEG) {
+    nkt_a = (Kc + 63) >> 6;
+    nkt_b = has_b ? (sg.Kc + 63) >> 6 : 0;
+  }
+  const int nkt = SK ? kseg : ((Kc + 63) >> 6) + nkt_b;
 
   // ---- staging: 8 units per K tile, one LDS-DMA per wave per unit (wave w -> unit rows 8w..8w+7) -----------------
   const auto rsP = __builtin_amdgcn_make_buffer_rsrc((void *)pr.P, 0, pr.p_bytes, 0x00020000);
   const auto rsQ = __builtin_amdgcn_make_buffer_rsrc((void *)pr.Q, 0, pr.q_bytes, 0x00020000);
+  const auto rsPb = SEG ? __builtin_amdgcn_make_buffer_rsrc((void *)sg.P, 0, sg.p_bytes, 0x00020000) : rsP;
+  const auto rsQb = SEG ? __builtin_amdgcn_make_buffer_rsrc((void *)sg.Q, 0, sg.q_bytes, 0x00020000) : rsQ;
   const int ur = wave * 8 + (lane >> 3);  // unit row this lane stages
   const int cp = lane & 7;                // LDS chunk position
   unsigned voff[8];                       // A0(0) A0(1) A1(0) A1(1) B0(0) B0(1) B1(0) B1(1)
@@ -139,9 +153,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs args) {
   // a (B, L1 + L2, N) gradient in place): the lane's row walks 64 rows per K tile; when it leaves its batch (q_rpb >= 64:
   // at most once per step) the cursor jumps over the rows between the batches.  One row counter per unit pair (B0 / B1
   // are staged in different phases).
-  const int q_rpb = Q_XC ? (int)pr.q_rpb() : 0;
+  int q_rpb = Q_XC ? (int)pr.q_rpb() : 0;
   const unsigned q_gap = (unsigned)((pr.q_bstride - q_rpb * ldq) * 2);
   int q_rl[2] = {ur, ur};
+  // SEG: the DMA streams as CURSORS (descriptor, step) per unit pair -- A0 (pair 0), A1 (pair 2), B0 / B1 (pairs 4, 6: staged
+  // together) -- that roll() below moves to the second source; the K loop's staging itself is the one-source code
+  auto rsP0 = rsP, rsP2 = rsP, rsQc = rsQ;
+  unsigned p_step0 = p_step, p_step2 = p_step;
 
   // stage the unit pair (u, u+1) of K tile `kt` into buffer kt & 1; past the last tile: out-of-range DMAs (no
   // traffic, they keep the vmcnt bookkeeping uniform; the buffer they zero is never read again)
@@ -151,8 +169,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs args) {
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
       const unsigned vo = live ? voff[u + d] : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(u < 4 ? rsP : rsQ, (lds_void_t *)(smem + base + d * 8192), 16, vo, 0, 0, 0);
-      voff[u + d] += (u < 4) ? p_step : q_step;
+      if constexpr (SEG) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(u < 4 ? (u < 2 ? rsP0 : rsP2) : rsQc, (lds_void_t *)(smem + base + d * 8192), 16, vo, 0, 0, 0);
+        voff[u + d] += (u < 4) ? (u < 2 ? p_step0 : p_step2) : q_step;
+      } else {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(u < 4 ? rsP : rsQ, (lds_void_t *)(smem + base + d * 8192), 16, vo, 0, 0, 0);
+        voff[u + d] += (u < 4) ? p_step : q_step;
+      }
     }
     if (Q_XC && u >= 4 && q_rpb != 0) {   // (workgroup-uniform branch)
       int &rl = q_rl[(u - 4) >> 1];
@@ -161,6 +184,31 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs args) {
       rl -= wrap ? q_rpb : 0;
       voff[u] += wrap ? q_gap : 0u;
       voff[u + 1] += wrap ? q_gap : 0u;
+    }
+  };
+  // SEG, workgroup-uniform, called only from the K tile on whose staging reaches segment b (the last nkt_b + 2 trips of the K
+  // loop): k1 = the K tile pair 2 stages next, k2 = the one pairs 0, 4 and 6 stage next.  A pair that arrives at the segment's
+  // first K tile is re-based on the second source -- the same two DMAs per stage_pair call before and after, so the counted
+  // waits of the K loop keep their meaning across the switch.  P: plain rows, re-based once.  Q: a batched-row view of ANY rows
+  // per batch (the twin case: 20): every lane maps its row of every K tile of the segment -- one division per lane per K tile,
+  // on the handful of K tiles of a second source -- and the q_rpb >= 64 cursor of segment a is switched off.
+  auto roll = [&](int k1, int k2) {
+    const int c = cp ^ (xg(ur) << 1);
+    const unsigned pcol = (unsigned)(ur * sg.ldp + i0 + c * 8), step_b = (unsigned)(64 * sg.ldp * 2);
+    if (k1 == nkt_a) {
+      voff[2] = (pcol + 64u) * 2u; voff[3] = (pcol + 192u) * 2u;    // unit U: g = U & 1, half = U >> 1 -> + g * 128 + half * 64
+      rsP2 = rsPb; p_step2 = step_b;
+    }
+    if (k2 == nkt_a) {
+      voff[0] = pcol * 2u; voff[1] = (pcol + 128u) * 2u;
+      rsP0 = rsPb; p_step0 = step_b;
+      rsQc = rsQb; q_rpb = 0;
+    }
+    if (k2 >= nkt_a) {
+      const unsigned qcol = mapped_row((k2 - nkt_a) * 64 + ur, sg.ldq, sg.q_rpb(), sg.q_bstride) +
+                            (unsigned)(j0 + (c >> 2) * 64 + (c & 3) * 8);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) voff[4 + u] = (qcol + (unsigned)((u & 1) * 128 + (u >> 1) * 32)) * 2u;
     }
   };
 
@@ -205,7 +253,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs args) {
   }
 
   // ---- prologue: tile 0 whole, then A0 B0 B1 of tile 1 (its A1 is staged by X(0)) ---------------------------------------
-  stage_pair(0, 0); stage_pair(4, 0); stage_pair(6, 0); stage_pair(2, 0); stage_pair(0, 1); stage_pair(4, 1); stage_pair(6, 1);
+  stage_pair(0, 0); stage_pair(4, 0); stage_pair(6, 0); stage_pair(2, 0);
+  if constexpr (SEG) {
+    if (has_b && 1 >= nkt_a) roll(-1, 1);   // (a one-K-tile segment a: tile 1 is segment b's first)
+  }
+  stage_pair(0, 1); stage_pair(4, 1); stage_pair(6, 1);
   if (GTAB) gelu_tab_fill<EPI == EPI_DGELU>(s_gtab, tid, 512);  // under the prologue's DMA latency; read after the K loop
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // A0 B0 B1 of tile 0 have landed (behind them: A1(0) and tile 1's six)
   BQ_BARRIER();
@@ -239,6 +291,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs args) {
   // a(t+1) + b(t+1) = 8 behind it -- vmcnt(8) both times, a stage is waited for one K tile after it was issued.
   for (int kt = 0; kt < nkt; ++kt) {
     const unsigned buf = smem_lds + (unsigned)((kt & 1) * 65536);   // (asm reads: gemm_common.h, read_frag_asm)
+    if constexpr (SEG) {
+      if (has_b && kt + 2 >= nkt_a) roll(kt + 1, kt + 2);
+    }
     // ---- X: A0, B0, B1 -> Q00, Q01 ; stage A1(t+1)
     if (vA0) {
 #pragma unroll
@@ -1340,6 +1395,12 @@ extern "C" int bq_gemm_bf16(const bq_gemm_desc *d, int n, int flags, int epilogu
     ga.total_tiles = 0;
     while (done < n && ga.n < GEMM_MAX_PROBLEMS) {
       const bq_gemm_desc &s = d[done];
+      // BQ_GEMM_SECOND: an entry without `out` behind a problem is that problem's second row source; the pair takes two
+      // table entries of ONE launch (a launch holds at most GEMM_MAX_PROBLEMS / 2 two-source problems)
+      const bool has2 = (flags & BQ_GEMM_SECOND) && done + 1 < n && d[done + 1].out == nullptr;
+      if (has2 && ga.n + 2 > GEMM_MAX_PROBLEMS) break;
+      BQ_REQUIRE(s.out || !(flags & BQ_GEMM_SECOND), BQ_EINVAL,
+                 "bq_gemm_bf16: BQ_GEMM_SECOND: entry %d has no out and no primary problem in front of it", done);
       BQ_REQUIRE(s.P && s.Q && s.out, BQ_EINVAL, "bq_gemm_bf16: null operand (problem %d)", done);
       BQ_REQUIRE(s.Ni > 0 && s.Nj > 0 && s.Kc > 0, BQ_EINVAL, "bq_gemm_bf16: empty problem %d", done);
       BQ_REQUIRE(s.ldp % 8 == 0 && s.ldq % 8 == 0, BQ_EINVAL, "bq_gemm_bf16: operand leading dimensions must be multiples of 8 elements");
@@ -1419,6 +1480,46 @@ extern "C" int bq_gemm_bf16(const bq_gemm_desc *d, int n, int flags, int epilogu
       ga.total_tiles += g.tiles_i() * ((s.Nj + tj - 1) / tj) * (epilogue == EPI_BIAS_CE ? 1 : g.ksplit());
       ++ga.n;
       ++done;
+      if (has2) {
+        // the second row source: a continuation entry behind its primary (gemm_common.h, GemmProblem::flags) -- no tiles
+        const bq_gemm_desc &t = d[done];
+        BQ_REQUIRE(tile == 256 && pxc && qxc && f32 && epilogue == EPI_NONE, BQ_EINVAL,
+                   "bq_gemm_bf16: a second row source needs the weight-gradient form (P_XC | Q_XC | OUT_F32, epilogue NONE) on "
+                   "tile 256 (entry %d)", done);
+        BQ_REQUIRE(t.P && t.Q && ((uintptr_t)t.P % 16 == 0) && ((uintptr_t)t.Q % 16 == 0) && t.ldp % 8 == 0 && t.ldq % 8 == 0,
+                   BQ_EINVAL, "bq_gemm_bf16: second row source: null / unaligned operand or leading dimension (entry %d)", done);
+        BQ_REQUIRE(t.Ni == s.Ni && t.Nj == s.Nj && t.Kc > 0, BQ_EINVAL,
+                   "bq_gemm_bf16: second row source: Ni / Nj must equal the primary's (%d x %d against %d x %d), Kc > 0 (entry %d)",
+                   t.Ni, t.Nj, s.Ni, s.Nj, done);
+        BQ_REQUIRE(s.ksplit <= 1 && t.ksplit <= 1 && !t.accum && !t.bias && !t.out2 && !t.aux && !t.colsum && t.o_rpb == 0, BQ_EINVAL,
+                   "bq_gemm_bf16: second row source: no ksplit, and nothing but P, Q, their leading dimensions, Kc and the q map "
+                   "(entry %d)", done);
+        BQ_REQUIRE(t.q_rpb >= 0 && t.q_rpb <= 65535, BQ_EINVAL, "bq_gemm_bf16: second row source: q_rpb must be in 0..65535 (entry %d)", done);
+        const long pb2 = ((long)(t.Kc - 1) * t.ldp + t.Ni) * 2;
+        long qb2 = ((long)(t.Kc - 1) * t.ldq + t.Nj) * 2, q_reach = ((long)(t.Kc + 64) * t.ldq + t.Nj + 256) * 2;
+        if (t.q_rpb > 0) {   // any rows per batch: every lane maps its row (no q_rpb >= 64 rule for this segment)
+          BQ_REQUIRE(t.Kc % t.q_rpb == 0 && t.q_bstride % 8 == 0 && (long)t.q_bstride >= (long)t.q_rpb * t.ldq, BQ_EINVAL,
+                     "bq_gemm_bf16: second row source: q map: Kc = %d must be whole batches of q_rpb = %d rows, q_bstride %% 8 == 0 "
+                     "and >= q_rpb * ldq", t.Kc, t.q_rpb);
+          qb2 = ((t.Kc / t.q_rpb - 1) * (long)t.q_bstride + (long)(t.q_rpb - 1) * t.ldq + t.Nj) * 2;
+          // (the furthest element a lane of the padded last K tile may address: it must stay below the out-of-range sentinel)
+          q_reach = (((long)(t.Kc + 63) / t.q_rpb + 1) * t.q_bstride + (long)t.q_rpb * t.ldq + t.Nj + 256) * 2;
+        }
+        BQ_REQUIRE(pb2 + 256L * t.ldp * 2 < 0x7FFFFFFFL && q_reach < 0x7FFFFFFFL, BQ_EINVAL,
+                   "bq_gemm_bf16: second row source: operand larger than 2 GB (entry %d)", done);
+        g.flags |= 4;
+        GemmProblem &c = ga.p[ga.n];
+        c = GemmProblem{};
+        c.P = (const __bf16 *)t.P; c.Q = (const __bf16 *)t.Q;
+        c.ldp = t.ldp; c.ldq = t.ldq; c.Ni = t.Ni; c.Nj = t.Nj; c.Kc = t.Kc;
+        c.p_bytes = (unsigned)pb2; c.q_bytes = (unsigned)qb2;
+        c.q_bstride = t.q_bstride;
+        c.rpb_pack = t.q_rpb;
+        c.flags = 8;
+        c.tile0 = 0x7fffffff;
+        ++ga.n;
+        ++done;
+      }
     }
     BQ_REQUIRE(launch_gemm(ga, flags, epilogue, tile, st) == 0, BQ_EINVAL,
                "bq_gemm_bf16: unsupported combination flags=%d epilogue=%d tile=%d", flags, epilogue, tile);

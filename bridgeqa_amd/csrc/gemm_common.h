@@ -39,7 +39,11 @@ struct GemmProblem {
   int tiles_ks;        // tiles along i | ksplit << 16.  ksplit > 1 (fp32 out, small-tile kernel): the contraction is cut
                        // into ksplit pieces, one workgroup each, accumulated with fp32 atomics into a zero-initialised `out`
   int flags;           // bit 0: bias is bf16; bit 1: accum (fp32 out, small-tile kernel: add to `out` / `colsum` with fp32
-                       // atomics instead of storing)
+                       // atomics instead of storing); bit 2: the NEXT table entry is this problem's second contraction
+                       // segment (256-tile weight-gradient form: dW = Qa^T Pa + Qb^T Pb); bit 3: this entry IS such a
+                       // continuation -- P, Q, ldp, ldq, Kc, p_bytes, q_bytes, q_rpb, q_bstride of the second row source, no
+                       // tiles of its own (tile0 = INT_MAX: the workgroup -> problem search never lands on it)
+  __host__ __device__ __forceinline__ int has_seg() const { return (flags >> 2) & 1; }
   __host__ __device__ __forceinline__ int q_rpb() const { return rpb_pack & 0xffff; }
   __host__ __device__ __forceinline__ int o_rpb() const { return (int)((unsigned)rpb_pack >> 16); }
   __host__ __device__ __forceinline__ int tiles_i() const { return tiles_ks & 0xffff; }

@@ -113,6 +113,7 @@ _PLAN_CACHE = {}
 _PLAN_WGRAD = [True]
 _QSUM = [True]
 _QSUM64 = [True]
+_TWO_SOURCE = [True]   # (tools / tests flip it: False = every second row source through the 64-tile adder launch, as before)
 
 
 def plan_big_launches(tiles, cus, max_problems=36, moved_cost=0.011):
@@ -166,6 +167,32 @@ def plan_big_launches(tiles, cus, max_problems=36, moved_cost=0.011):
     return plan
 
 
+def split_for_table(group, two, max_entries=36):
+    """One planned 256-tile launch whose problems `group` (longest contraction first) need more kernel-argument entries than a
+    launch has -- a problem with a second row source takes two (two[k]) -- as the fewest launches that fit, the problems DEALT
+    round-robin: every launch gets the same mix of long and short contractions.  Cutting the list where the table is full (what
+    the library does with it) leaves all the long ones in the first launch: the twin K/V flush (12 x 257 and 12 x 64 K tiles,
+    18 tiles each) then ran 324 tiles with 41 long ones on each of the first XCDs' 32 CUs -- two long rounds -- and a
+    108-tile tail, 880 + 126 us under the profiler; dealt, each launch is 216 tiles, resident at once: 415 + 410 us
+    (profiles/wgrad_two_source.md)."""
+    entries = len(group) + sum(two)
+    n = -(-entries // max_entries)
+    if n <= 1:
+        return [list(group)]
+    chunks = [group[c::n] for c in range(n)]
+    sizes = [len(group[c::n]) + sum(two[c::n]) for c in range(n)]
+    if max(sizes) > max_entries:   # (an uneven deal of mixed problems: fall back to cutting the list in order)
+        chunks, cur, used = [], [], 0
+        for k, t in zip(group, two):
+            if used + 1 + t > max_entries:
+                chunks.append(cur)
+                cur, used = [], 0
+            cur.append(k)
+            used += 1 + t
+        chunks.append(cur)
+    return [c for c in chunks if c]
+
+
 def _nrows(t):
     """rows of a GEMM row operand: (rows, cols), or a (batch, rows, cols) batched-row view (_ext._mat_rows)"""
     return t.shape[0] if t.dim() == 2 else t.shape[0] * t.shape[1]
@@ -174,7 +201,8 @@ def _nrows(t):
 def flush_deferred_items(items):
     """items: (dY, X, weights, biases[, primary]) records.  `primary` (optional) = index of ANOTHER record of the same
     weights: this record's rows are a second row source of that weight gradient (the twin K/V projection reads image
-    tokens and the other stream's states, _TwinKVFn) and are ADDED to it by a launch behind the primary one."""
+    tokens and the other stream's states, _TwinKVFn): summed inside the primary's launch when that is the 256 x 256 kernel's,
+    otherwise ADDED to it by a launch behind the primary one."""
     if not items:
         return
     from . import _ext
@@ -201,6 +229,18 @@ def flush_deferred_items(items):
         plan_groups, moved = plan_big_launches(tiles, cus * (256 // tj))
         groups = [[big[j] for j in g] for g in plan_groups]
         small = small + [big[j] for j in moved]
+    # a second row source whose primary runs on the 256 x 256 kernel rides in that launch as a second contraction segment
+    # (_ext.gemm_grouped P2 / Q2: its K tiles follow the primary's in the same workgroups, no pass over the stored gradient, no
+    # atomics; one workgroup owns a tile, so the sum is fixed-order in every mode).  The planner above counted tiles without
+    # them -- a segment adds none; the library splits a launch after 18 such pairs.
+    attach = {}
+    if _TWO_SOURCE[0] and _DW_TILE[0] == 256:
+        on_big = {k for g in groups for k in g}
+        for k in second:
+            if items[k][4] in on_big and (items[k][3] is None or _QSUM[0]):   # (the bias gradient comes from the same launch)
+                attach.setdefault(items[k][4], k)   # (a kernel problem carries ONE segment: further sources keep the adder)
+        second = [k for k in second if attach.get(items[k][4]) != k]
+        groups = [c for g in groups for c in split_for_table(g, [k in attach for k in g])]
     dbs = {}
     for tile, idx_groups in ((_DW_TILE[0], groups), (_SHORT_DW_TILE[0], [mid] if mid else []), (64, [small] if small else [])):
         for idx in idx_groups:
@@ -209,6 +249,8 @@ def flush_deferred_items(items):
                 g2, x2 = items[k][0], items[k][1]
                 dws[k] = torch.empty(g2.shape[-1], x2.shape[-1], dtype=torch.float32, device=g2.device)
                 pr = dict(P=x2, Q=g2, out=dws[k])
+                if k in attach:
+                    pr.update(P2=items[attach[k]][1], Q2=items[attach[k]][0])
                 if items[k][3] is not None and _QSUM[0] and (tile != 64 or _QSUM64[0]):
                     # the bias gradient (column sums of dY) from the same launch: four more MFMAs per K tile in a third
                     # of the workgroups instead of a second pass over dY (csrc/gemm.hip, QSUM)

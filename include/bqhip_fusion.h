@@ -403,6 +403,14 @@ BQ_API int bq_fuse_point_features(const int *pix, const float *feat, float *out,
                          summed in piece order by bq_gemm_splitk_fold_det; no colsum, accum or output map with it), accum adds
                          with a plain load and store.  Refused: column sums of a bf16 output (bq_colsum_grouped_det_bf16 takes
                          them), tile 128 while a stream-K mode is on. */
+#define BQ_GEMM_SECOND 32 /* additive to ABI 6 (bq_gemm_desc keeps its 22 members: the second source travels as an entry of the
+                            array).  Weight-gradient form on tile 256 only (P_XC | Q_XC | OUT_F32, epilogue NONE): an entry whose
+                            `out` is NULL is the SECOND ROW SOURCE of the entry in front of it, dW = Qa^T Pa + Qb^T Pb in one pass
+                            -- its K tiles follow the primary's in the same workgroups, plain stores, colsum takes both sources'
+                            rows.  Read of such an entry: P, Q, ldp, ldq, Kc (its rows), Ni / Nj (equal to the primary's), q_rpb /
+                            q_bstride (ANY rows per batch, e.g. the 20 text rows of each sample's (P + 20)-row gradient);
+                            everything else must be zero, neither entry may set ksplit.  The pair takes two of the
+                            bq_gemm_max_problems() entries of a launch.  Refused (BQ_EINVAL) on every other form and tile. */
 #define BQ_GEMM_EPI_NONE 0
 #define BQ_GEMM_EPI_BIAS 1
 #define BQ_GEMM_EPI_BIAS_GELU 2
