@@ -34,6 +34,7 @@ if _lib.bq_abi_version() != ABI_VERSION:
 _cabi.bind(_lib)
 _cabi.bind(_lib, _cabi.ADDITIVE_PROTOS)
 _cabi.bind(_lib, _cabi.EXTENSION_PROTOS)
+_cabi.bind(_lib, _cabi.MCAN_PROTOS)
 
 # ---- the deterministic training mode (bridgeqa_amd.set_deterministic) ------------------------------------------------------------
 # Every site of the training path where float atomics from several workgroups met on one address, the entry point that takes it in
@@ -626,6 +627,131 @@ def lstm_bwd(dy, dh_last, gates, cells, w_hh, lens, reverse=False):
         _check(_lib.bq_lstm_bwd(_p(dy), _p(dh_last), _p(gates), _p(cells), _p(w_hh), _p(lens), _p(dgx), B, t_out, H,
                                 int(bool(reverse)), _stream()), "lstm_bwd")
     return dgx
+
+
+# ---- the row operators of the MCAN blocks: residual LayerNorm and AttFlat pooling (csrc/mcan.hip, include/bqhip_mcan.h) -----------
+MCAN_MAX_H = _cabi.ADDITIVE_DEFINES["BQ_MCAN_MAX_H"]
+MCAN_MAX_N = _cabi.ADDITIVE_DEFINES["BQ_MCAN_MAX_N"]
+MCAN_MAX_G = _cabi.ADDITIVE_DEFINES["BQ_MCAN_MAX_G"]
+MCAN_CALLS = [0, 0, 0, 0]  # launches of mcan_ln_fwd / mcan_ln_bwd / attflat_pool_fwd / attflat_pool_bwd so far
+
+
+def mcan_hidden_ok(H):
+    """the row lengths the kernels of csrc/mcan.hip are built for: multiples of 64 from 64 to MCAN_MAX_H"""
+    return 64 <= H <= MCAN_MAX_H and H % 64 == 0
+
+
+def _mcan_operands(what, items):
+    """items: (tensor or None, shape, name, dtype); a CPU tensor raises first, as everywhere in this module"""
+    for t, _, n, _ in items:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("%s: %s: CPU not supported" % (what, n))
+    for t, shape, n, dtype in items:
+        if t is not None:
+            _lstm_operand(t, shape, "%s: %s" % (what, n), dtype)
+    _same_device(*[t for t, _, _, _ in items if t is not None])
+
+
+def _mcan_hidden(H, what):
+    if not mcan_hidden_ok(H):
+        raise RuntimeError("%s: row length %d is not built (a multiple of 64 in [64, %d])" % (what, H, MCAN_MAX_H))
+
+
+def mcan_ln_fwd(x, s, a2, b2, eps):
+    """MCAN's LayerNorm of z = x + s (s None: z = x): y = a2 (z - mean) / (sigma + eps) + b2 with the unbiased deviation.  x, s:
+    f32 (M, H); a2, b2: f32 (H).  Returns y (M, H), mean (M), sigma (M) -- what mcan_ln_bwd reads."""
+    if not x.is_cuda:
+        raise RuntimeError("mcan_ln_fwd: x: CPU not supported")
+    if x.dim() != 2:
+        raise RuntimeError("mcan_ln_fwd: x must be (M, H)")
+    M, H = x.shape
+    _mcan_operands("mcan_ln_fwd", ((x, (M, H), "x", torch.float32), (s, (M, H), "s", torch.float32),
+                                   (a2, (H,), "a2", torch.float32), (b2, (H,), "b2", torch.float32)))
+    _mcan_hidden(H, "mcan_ln_fwd")
+    with torch.cuda.device(x.device):
+        y = torch.empty_like(x)
+        mean = torch.empty(M, dtype=torch.float32, device=x.device)
+        sigma = torch.empty(M, dtype=torch.float32, device=x.device)
+        MCAN_CALLS[0] += 1
+        _check(_lib.bqm_mcan_ln_fwd(_p(x), _p(s), _p(a2), _p(b2), _p(y), _p(mean), _p(sigma), M, H, float(eps), _stream()),
+               "mcan_ln_fwd")
+    return y, mean, sigma
+
+
+def mcan_ln_bwd(dy, x, s, a2, mean, sigma, eps):
+    """gradients of mcan_ln_fwd.  Returns dz (M, H) -- the gradient of x and of s alike -- and dab (2, H) = [da2, db2], stored
+    (not accumulated) by a fixed-order fold over a slab allocated here."""
+    if not dy.is_cuda:
+        raise RuntimeError("mcan_ln_bwd: dy: CPU not supported")
+    if dy.dim() != 2:
+        raise RuntimeError("mcan_ln_bwd: dy must be (M, H)")
+    M, H = dy.shape
+    _mcan_operands("mcan_ln_bwd", ((dy, (M, H), "dy", torch.float32), (x, (M, H), "x", torch.float32),
+                                   (s, (M, H), "s", torch.float32), (a2, (H,), "a2", torch.float32),
+                                   (mean, (M,), "mean", torch.float32), (sigma, (M,), "sigma", torch.float32)))
+    _mcan_hidden(H, "mcan_ln_bwd")
+    with torch.cuda.device(dy.device):
+        dz = torch.empty_like(dy)
+        if M == 0:
+            return dz, torch.zeros(2, H, dtype=torch.float32, device=dy.device)
+        dab = torch.empty(2, H, dtype=torch.float32, device=dy.device)
+        slab = torch.empty(_lib.bqm_mcan_ln_bwd_slab_floats(M, H), dtype=torch.float32, device=dy.device)
+        MCAN_CALLS[1] += 1
+        _check(_lib.bqm_mcan_ln_bwd(_p(dy), _p(x), _p(s), _p(a2), _p(mean), _p(sigma), _p(dz), _p(dab), _p(slab), M, H,
+                                    float(eps), _stream()), "mcan_ln_bwd")
+    return dz, dab
+
+
+def _pool_extents(x, what):
+    if x.dim() != 3:
+        raise RuntimeError("%s: x must be (B, N, H)" % what)
+    return x.shape
+
+
+def _pool_limits(N, G, H, what):
+    _mcan_hidden(H, what)
+    if not (1 <= N <= MCAN_MAX_N and 1 <= G <= MCAN_MAX_G):
+        raise RuntimeError("%s: N %d, G %d are not built (1 <= N <= %d, 1 <= G <= %d)" % (what, N, G, MCAN_MAX_N, MCAN_MAX_G))
+
+
+def attflat_pool_fwd(x, logits, hide=None):
+    """AttFlat's tail: p = softmax over the keys of (hide ? -1e9 : logits), out[b, g H + h] = sum_n p[b, n, g] x[b, n, h].
+    x: f32 (B, N, H); logits: f32 (B, N, G); hide: uint8 (B, N), non-zero = hidden, or None.  Returns out (B, G H), p (B, N, G)."""
+    if not x.is_cuda:
+        raise RuntimeError("attflat_pool_fwd: x: CPU not supported")
+    B, N, H = _pool_extents(x, "attflat_pool_fwd")
+    if logits.dim() != 3:
+        raise RuntimeError("attflat_pool_fwd: logits must be (B, N, G)")
+    G = logits.shape[2]
+    _mcan_operands("attflat_pool_fwd", ((x, (B, N, H), "x", torch.float32), (logits, (B, N, G), "logits", torch.float32),
+                                        (hide, (B, N), "hide", torch.uint8)))
+    _pool_limits(N, G, H, "attflat_pool_fwd")
+    with torch.cuda.device(x.device):
+        out = torch.empty(B, G * H, dtype=torch.float32, device=x.device)
+        p = torch.empty(B, N, G, dtype=torch.float32, device=x.device)
+        MCAN_CALLS[2] += 1
+        _check(_lib.bqm_attflat_pool_fwd(_p(x), _p(logits), _p(hide), _p(out), _p(p), B, N, G, H, _stream()), "attflat_pool_fwd")
+    return out, p
+
+
+def attflat_pool_bwd(dout, x, p, hide=None):
+    """gradients of attflat_pool_fwd: dx (B, N, H) and dlogits (B, N, G), exactly 0 where hide is set"""
+    if not dout.is_cuda:
+        raise RuntimeError("attflat_pool_bwd: dout: CPU not supported")
+    B, N, H = _pool_extents(x, "attflat_pool_bwd")
+    if p.dim() != 3:
+        raise RuntimeError("attflat_pool_bwd: p must be (B, N, G)")
+    G = p.shape[2]
+    _mcan_operands("attflat_pool_bwd", ((dout, (B, G * H), "dout", torch.float32), (x, (B, N, H), "x", torch.float32),
+                                        (p, (B, N, G), "p", torch.float32), (hide, (B, N), "hide", torch.uint8)))
+    _pool_limits(N, G, H, "attflat_pool_bwd")
+    with torch.cuda.device(x.device):
+        dx = torch.empty_like(x)
+        dlogits = torch.empty_like(p)
+        MCAN_CALLS[3] += 1
+        _check(_lib.bqm_attflat_pool_bwd(_p(dout), _p(x), _p(p), _p(hide), _p(dx), _p(dlogits), B, N, G, H, _stream()),
+               "attflat_pool_bwd")
+    return dx, dlogits
 
 
 # ---- training-scene preparation: sample, augment, vote labels (csrc/scene_prep.hip, include/bqhip_scene.h) -----------------------

@@ -97,7 +97,7 @@ def lang_branch_forward(module, data_dict, object_feat, object_mask, use_lang_cl
         data_dict["cluster_ref"] = module.object_cls(conf).squeeze(-1)
     lang_feat = module.attflat_lang(lang_feat, lang_mask)
     object_feat = module.attflat_visual(object_feat, object_mask, 0, 100)   # (ScanQA.att_pdrop: 0, no flag in train.py)
-    fuse_feat = module.fusion_norm(lang_feat + object_feat)
+    fuse_feat = module.fusion_norm(lang_feat, object_feat)
     data_dict["fuse_feat"] = fuse_feat.clone()
     if use_lang_cls:
         data_dict["lang_scores"] = module.lang_cls(fuse_feat)

@@ -11,12 +11,82 @@ hotpath.ScanQAHotPath(use_blip=False, lang_branch=True)): torch compositions ove
 Reference quirks kept on purpose (parity, not opinion):
   * LayerNorm divides by (std + eps) with the UNBIASED standard deviation (torch.std), not sqrt(var + eps);
   * masks are boolean with True = "hide this key" (scores.masked_fill(mask, -1e9)).
+
+The fused route (set_fused / BQ_MCAN_FUSED=1, default off).  The two launch-bound compositions of these blocks -- LayerNorm,
+always applied to a residual sum, ~11 launches forward; AttFlat's masked_fill / softmax / weighted sums / cat -- have kernels in
+csrc/mcan.hip (include/bqhip_mcan.h states their arithmetic).  With the switch on, fp32 device tensors of an eligible size take
+them through one autograd Function each; everything else, and everything with the switch off, runs the compositions below
+unchanged.  nn.Dropout stays a torch op on both routes, so one seed gives both the same masks.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+_FUSED = os.environ.get("BQ_MCAN_FUSED", "0") == "1"
+
+
+def set_fused(flag):
+    """route LayerNorm and AttFlat's pooling through csrc/mcan.hip where eligible; returns the previous setting"""
+    global _FUSED
+    prev, _FUSED = _FUSED, bool(flag)
+    return prev
+
+
+def fused_enabled():
+    return _FUSED
+
+
+def _f32_cuda(*ts):
+    return all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+class _ResidualLayerNormFn(torch.autograd.Function):
+    """a_2 (z - mean) / (sigma + eps) + b_2 over z = x + s on bqm_mcan_ln_fwd / bqm_mcan_ln_bwd"""
+
+    @staticmethod
+    def forward(ctx, x, s, a2, b2, eps):
+        from . import _ext
+        H = x.shape[-1]
+        x2 = x.detach().reshape(-1, H).contiguous()
+        s2 = s.detach().reshape(-1, H).contiguous() if s is not None else None
+        a2d = a2.detach().contiguous()
+        y, mean, sigma = _ext.mcan_ln_fwd(x2, s2, a2d, b2.detach().contiguous(), eps)
+        ctx.save_for_backward(x2, s2, a2d, mean, sigma)
+        ctx.eps = eps
+        return y.view(x.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        from . import _ext
+        x2, s2, a2d, mean, sigma = ctx.saved_tensors
+        dz, dab = _ext.mcan_ln_bwd(dy.reshape(x2.shape).contiguous(), x2, s2, a2d, mean, sigma, ctx.eps)
+        dz = dz.view(dy.shape)
+        return dz, (dz if s2 is not None else None), dab[0], dab[1], None
+
+
+class _AttFlatPoolFn(torch.autograd.Function):
+    """softmax over the keys of the (masked) glimpse logits and the glimpses' weighted sums on bqm_attflat_pool_fwd / _bwd"""
+
+    @staticmethod
+    def forward(ctx, x, logits, hide):
+        from . import _ext
+        xc, lc = x.detach().contiguous(), logits.detach().contiguous()
+        out, p = _ext.attflat_pool_fwd(xc, lc, hide)
+        ctx.save_for_backward(xc, p, hide)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import _ext
+        xc, p, hide = ctx.saved_tensors
+        dx, dlogits = _ext.attflat_pool_bwd(dout.contiguous(), xc, p, hide)
+        return dx, dlogits, None
 
 
 class FC(nn.Module):
@@ -55,7 +125,20 @@ class LayerNorm(nn.Module):
         self.a_2 = nn.Parameter(torch.ones(size))
         self.b_2 = nn.Parameter(torch.zeros(size))
 
-    def forward(self, x):
+    def _fused_ok(self, x, residual):
+        if not (_FUSED and _f32_cuda(x, self.a_2, self.b_2) and x.dim() >= 1 and x.numel() > 0):
+            return False
+        if residual is not None and not (_f32_cuda(residual) and residual.shape == x.shape and residual.device == x.device):
+            return False
+        from . import _ext
+        return _ext.mcan_hidden_ok(x.shape[-1]) and self.a_2.shape == (x.shape[-1],) and self.a_2.device == x.device
+
+    def forward(self, x, residual=None):
+        """LayerNorm(x + residual); the sum is formed inside the kernel on the fused route"""
+        if self._fused_ok(x, residual):
+            return _ResidualLayerNormFn.apply(x, residual, self.a_2, self.b_2, self.eps)
+        if residual is not None:
+            x = x + residual
         centred = x - x.mean(-1, keepdim=True)
         n = x.shape[-1]
         std = centred.pow(2).sum(-1, keepdim=True).div(max(n - 1, 1)).sqrt()
@@ -110,8 +193,8 @@ class SA(nn.Module):
         self.dropout2, self.norm2 = nn.Dropout(pdrop), LayerNorm(hidden_size)
 
     def forward(self, x, x_mask):
-        x = self.norm1(x + self.dropout1(self.mhatt(x, x, x, x_mask)))
-        return self.norm2(x + self.dropout2(self.ffn(x)))
+        x = self.norm1(x, self.dropout1(self.mhatt(x, x, x, x_mask)))
+        return self.norm2(x, self.dropout2(self.ffn(x)))
 
 
 class SGA(nn.Module):
@@ -127,9 +210,9 @@ class SGA(nn.Module):
         self.dropout3, self.norm3 = nn.Dropout(pdrop), LayerNorm(hidden_size)
 
     def forward(self, x, y, x_mask, y_mask, att_pdrop=None, att_drop_topk=None):
-        x = self.norm1(x + self.dropout1(self.mhatt1(x, x, x, x_mask)))
-        x = self.norm2(x + self.dropout2(self.mhatt2(y, y, x, y_mask, att_pdrop, att_drop_topk)))
-        return self.norm3(x + self.dropout3(self.ffn(x)))
+        x = self.norm1(x, self.dropout1(self.mhatt1(x, x, x, x_mask)))
+        x = self.norm2(x, self.dropout2(self.mhatt2(y, y, x, y_mask, att_pdrop, att_drop_topk)))
+        return self.norm3(x, self.dropout3(self.ffn(x)))
 
 
 class AttFlat(nn.Module):
@@ -143,10 +226,23 @@ class AttFlat(nn.Module):
         self.flat_glimpses = flat_glimpses
         self.linear_merge = nn.Linear(hidden_size * flat_glimpses, flat_out_size)
 
+    def _fused_ok(self, x, att, x_mask):
+        if not (_FUSED and _f32_cuda(x, att) and x.dim() == 3 and x.numel() > 0):
+            return False
+        if x_mask is not None and not (x_mask.dtype == torch.bool and x_mask.is_cuda and x_mask.device == x.device
+                                       and x_mask.numel() == x.shape[0] * x.shape[1]):
+            return False
+        from . import _ext
+        return (_ext.mcan_hidden_ok(x.shape[2]) and 1 <= x.shape[1] <= _ext.MCAN_MAX_N
+                and 1 <= self.flat_glimpses <= _ext.MCAN_MAX_G)
+
     def forward(self, x, x_mask, att_pdrop=0, att_drop_topk=100):
         if att_pdrop > 0:
             raise NotImplementedError("AttFlat: att_pdrop > 0 (top-k score masking) is not supported")
         att = self.mlp(x)
+        if self._fused_ok(x, att, x_mask):
+            hide = x_mask.reshape(x.shape[0], x.shape[1]).contiguous().view(torch.uint8) if x_mask is not None else None
+            return self.linear_merge(_AttFlatPoolFn.apply(x, att, hide))
         if x_mask is not None:
             att = att.masked_fill(x_mask.squeeze(1).squeeze(1).unsqueeze(2), -1e9)
         att = F.softmax(att, dim=1)

@@ -14,6 +14,7 @@
 #include "bqhip_scene.h" /* bq_scene_boxes / bq_scene_sample / bq_scene_votes: additive to ABI 6 */
 #include "bqhip_view.h"  /* bq_view_prep: additive to ABI 6 */
 #include "bqhip_beam.h"  /* bqx_beam_step: additive to ABI 6 */
+#include "bqhip_mcan.h"  /* bqm_mcan_ln_* / bqm_attflat_pool_*: additive to ABI 6 */
 
 #ifdef __cplusplus
 extern "C" {
