@@ -23,7 +23,7 @@ _POINTEES = set(_SCALARS) | {"void", "char", "unsigned char", "long long"}   # w
 _TOP = re.compile(r'\s*(?:#([^\n]*)|extern\s+"C"\s*\{|\}|typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;|BQ_API\b([^;]*);)')
 _FIRST = re.compile(r"((?:\w+\s+)*?\w+)(?:\s+|\s*(\*+)\s*)(\w+)\s*(?:\[(\d+)\])?")   # `const float *gamma`, `bq_x layers[3]`
 _NEXT = re.compile(r"(\**)\s*(\w+)\s*(?:\[(\d+)\])?")                        # `*beta` after a comma
-_FUNC = re.compile(r"((?:\w+\s+)+?)(\**)\s*(bq[xm]?_\w+)\s*\(([^()]*)\)")
+_FUNC = re.compile(r"((?:\w+\s+)+?)(\**)\s*(bq[xmh]?_\w+)\s*\(([^()]*)\)")
 
 
 def _ctype(base, stars, structs, decl, ret=False):
@@ -101,7 +101,7 @@ PROTOS, STRUCTS, DEFINES = parse(_read_headers())
 
 # Entry points added to ABI 6 after tests/test_cabi_cpu.py counted the two headers above by hand: they live in headers of their
 # own (bqhip_fusion.h includes them) and in a table of their own, derived by the same parser.  bind(lib, ADDITIVE_PROTOS).
-ADDITIVE_HEADERS = ("bqhip_lstm.h", "bqhip_scene.h", "bqhip_view.h", "bqhip_beam.h", "bqhip_mcan.h")
+ADDITIVE_HEADERS = ("bqhip_lstm.h", "bqhip_scene.h", "bqhip_view.h", "bqhip_beam.h", "bqhip_mcan.h", "bqhip_mhatt.h")
 _additive, ADDITIVE_STRUCTS, ADDITIVE_DEFINES = parse(_read_headers(ADDITIVE_HEADERS))
 ADDITIVE_PROTOS = {n: p for n, p in _additive.items() if n.startswith("bq_")}
 # Entry points added after tests/test_cabi_cpu.py took its census of the library's bq_ symbols (103 with the table above) are named
@@ -112,6 +112,9 @@ EXTENSION_PROTOS = {n: p for n, p in _additive.items() if n.startswith("bqx_")}
 # the MCAN blocks (bqhip_mcan.h, csrc/mcan.hip) carry a family prefix of their own, bqm_: same header rules, same parser, same
 # compile-against-the-declaration.  bind(lib, MCAN_PROTOS).
 MCAN_PROTOS = {n: p for n, p in _additive.items() if n.startswith("bqm_")}
+# The bqm_ symbols are counted too (tests/test_mcan_rows_cpu.py holds them to the five row operators), so the attention core of
+# MHAtt (bqhip_mhatt.h, csrc/mhatt.hip) is a family of its own again, bqh_.  bind(lib, MHATT_PROTOS).
+MHATT_PROTOS = {n: p for n, p in _additive.items() if n.startswith("bqh_")}
 
 
 def bind(lib, names=None):
@@ -122,4 +125,4 @@ def bind(lib, names=None):
         except AttributeError:
             raise ImportError("bridgeqa_amd: libbqhip.so has no %s, which include/ declares (stale library: "
                               "python -m bridgeqa_amd.build --force)" % name) from None
-        fn.restype, fn.argtypes = next(t[name] for t in (PROTOS, ADDITIVE_PROTOS, EXTENSION_PROTOS, MCAN_PROTOS) if name in t)
+        fn.restype, fn.argtypes = next(t[name] for t in (PROTOS, ADDITIVE_PROTOS, EXTENSION_PROTOS, MCAN_PROTOS, MHATT_PROTOS) if name in t)

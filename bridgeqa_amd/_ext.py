@@ -35,6 +35,7 @@ _cabi.bind(_lib)
 _cabi.bind(_lib, _cabi.ADDITIVE_PROTOS)
 _cabi.bind(_lib, _cabi.EXTENSION_PROTOS)
 _cabi.bind(_lib, _cabi.MCAN_PROTOS)
+_cabi.bind(_lib, _cabi.MHATT_PROTOS)
 
 # ---- the deterministic training mode (bridgeqa_amd.set_deterministic) ------------------------------------------------------------
 # Every site of the training path where float atomics from several workgroups met on one address, the entry point that takes it in
@@ -752,6 +753,70 @@ def attflat_pool_bwd(dout, x, p, hide=None):
         _check(_lib.bqm_attflat_pool_bwd(_p(dout), _p(x), _p(p), _p(hide), _p(dx), _p(dlogits), B, N, G, H, _stream()),
                "attflat_pool_bwd")
     return dx, dlogits
+
+
+# ---- the attention core of the MCAN blocks' MHAtt (csrc/mhatt.hip, include/bqhip_mhatt.h) -----------------------------------------
+MHATT_MAX_N = _cabi.ADDITIVE_DEFINES["BQ_MHATT_MAX_N"]
+MHATT_HEAD = (32, 64)
+MHATT_CALLS = [0, 0]  # launches of mhatt_fwd / mhatt_bwd so far
+
+
+def mhatt_ok(H, heads, Nq, Nk):
+    """the sizes the kernels of csrc/mhatt.hip are built for: H = heads d with d 32 or 64, 1 <= Nq, Nk <= MHATT_MAX_N"""
+    return heads >= 1 and H % heads == 0 and H // heads in MHATT_HEAD and 1 <= Nq <= MHATT_MAX_N and 1 <= Nk <= MHATT_MAX_N
+
+
+def _mhatt_extents(q, k, heads, what):
+    if q.dim() != 3 or k.dim() != 3:
+        raise RuntimeError("%s: q must be (B, Nq, H) and k (B, Nk, H)" % what)
+    B, Nq, H = q.shape
+    Nk, heads = k.shape[1], int(heads)
+    if not mhatt_ok(H, heads, Nq, Nk):
+        raise RuntimeError("%s: H %d, heads %d, Nq %d, Nk %d are not built (H / heads in %s, 1 <= Nq, Nk <= %d)" % (
+            what, H, heads, Nq, Nk, MHATT_HEAD, MHATT_MAX_N))
+    if B * heads > 65535:
+        raise RuntimeError("%s: B heads = %d is not built (at most 65535)" % (what, B * heads))
+    return B, heads, Nq, Nk, H
+
+
+def mhatt_fwd(q, k, v, hide, keep, heads):
+    """MHAtt's core on the linears' outputs as they stand.  q: f32 (B, Nq, H); k, v: f32 (B, Nk, H), head h in columns
+    [h d, (h + 1) d); hide: uint8 (B, Nk), non-zero = hidden key, or None; keep: f32 (B, heads, Nq, Nk), the dropout multiplier,
+    or None.  Returns out (B, Nq, H) = softmax(hide ? -1e9 : q k^T / sqrt d) keep v per head and p (B, heads, Nq, Nk), the
+    probabilities before keep -- what mhatt_bwd reads."""
+    if not q.is_cuda:
+        raise RuntimeError("mhatt_fwd: q: CPU not supported")
+    B, heads, Nq, Nk, H = _mhatt_extents(q, k, heads, "mhatt_fwd")
+    _mcan_operands("mhatt_fwd", ((q, (B, Nq, H), "q", torch.float32), (k, (B, Nk, H), "k", torch.float32),
+                                 (v, (B, Nk, H), "v", torch.float32), (hide, (B, Nk), "hide", torch.uint8),
+                                 (keep, (B, heads, Nq, Nk), "keep", torch.float32)))
+    with torch.cuda.device(q.device):
+        out = torch.empty_like(q)
+        p = torch.empty(B, heads, Nq, Nk, dtype=torch.float32, device=q.device)
+        MHATT_CALLS[0] += 1
+        _check(_lib.bqh_mhatt_fwd(_p(q), _p(k), _p(v), _p(hide), _p(keep), _p(out), _p(p), B, heads, Nq, Nk, H // heads,
+                                  _stream()), "mhatt_fwd")
+    return out, p
+
+
+def mhatt_bwd(dout, q, k, v, p, hide, keep, heads):
+    """gradients of mhatt_fwd from p as saved: dq (B, Nq, H), dk and dv (B, Nk, H), each element stored once in a fixed order of
+    additions; dq and dk pass nothing through a hidden key.  The (B, heads, Nq, Nk) workspace is allocated here."""
+    if not dout.is_cuda:
+        raise RuntimeError("mhatt_bwd: dout: CPU not supported")
+    B, heads, Nq, Nk, H = _mhatt_extents(q, k, heads, "mhatt_bwd")
+    _mcan_operands("mhatt_bwd", ((dout, (B, Nq, H), "dout", torch.float32), (q, (B, Nq, H), "q", torch.float32),
+                                 (k, (B, Nk, H), "k", torch.float32), (v, (B, Nk, H), "v", torch.float32),
+                                 (p, (B, heads, Nq, Nk), "p", torch.float32), (hide, (B, Nk), "hide", torch.uint8),
+                                 (keep, (B, heads, Nq, Nk), "keep", torch.float32)))
+    d = H // heads
+    with torch.cuda.device(dout.device):
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        ws = torch.empty(max(1, _lib.bqh_mhatt_bwd_ws_floats(B, heads, Nq, Nk, d)), dtype=torch.float32, device=dout.device)
+        MHATT_CALLS[1] += 1
+        _check(_lib.bqh_mhatt_bwd(_p(dout), _p(q), _p(k), _p(v), _p(p), _p(hide), _p(keep), _p(dq), _p(dk), _p(dv), _p(ws), B,
+                                  heads, Nq, Nk, d, _stream()), "mhatt_bwd")
+    return dq, dk, dv
 
 
 # ---- training-scene preparation: sample, augment, vote labels (csrc/scene_prep.hip, include/bqhip_scene.h) -----------------------

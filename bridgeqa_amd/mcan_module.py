@@ -17,6 +17,12 @@ always applied to a residual sum, ~11 launches forward; AttFlat's masked_fill / 
 csrc/mcan.hip (include/bqhip_mcan.h states their arithmetic).  With the switch on, fp32 device tensors of an eligible size take
 them through one autograd Function each; everything else, and everything with the switch off, runs the compositions below
 unchanged.  nn.Dropout stays a torch op on both routes, so one seed gives both the same masks.
+
+The fused attention route (set_fused_attention / BQ_MCAN_ATT=1, default off; independent of the switch above).  MHAtt's core --
+scores, division, masked_fill, softmax, dropout, the product with V, transpose().contiguous(), 9 device kernels forward and
+11 backward per site -- has kernels in csrc/mhatt.hip (include/bqhip_mhatt.h states their arithmetic): one launch forward, two
+backward, reading the three linears' outputs in place and writing the layout linear_merge reads.  The dropout multiplier is
+drawn by MHAtt.dropout itself on a tensor of ones of the composition's shape, at the same point of the random stream.
 """
 import math
 import os
@@ -38,6 +44,20 @@ def set_fused(flag):
 
 def fused_enabled():
     return _FUSED
+
+
+_FUSED_ATT = os.environ.get("BQ_MCAN_ATT", "0") == "1"
+
+
+def set_fused_attention(flag):
+    """route MHAtt's attention core through csrc/mhatt.hip where eligible; returns the previous setting"""
+    global _FUSED_ATT
+    prev, _FUSED_ATT = _FUSED_ATT, bool(flag)
+    return prev
+
+
+def fused_attention_enabled():
+    return _FUSED_ATT
 
 
 def _f32_cuda(*ts):
@@ -87,6 +107,27 @@ class _AttFlatPoolFn(torch.autograd.Function):
         xc, p, hide = ctx.saved_tensors
         dx, dlogits = _ext.attflat_pool_bwd(dout.contiguous(), xc, p, hide)
         return dx, dlogits, None
+
+
+class _MHAttCoreFn(torch.autograd.Function):
+    """softmax(hide ? -1e9 : q k^T / sqrt d) keep v per head on bqh_mhatt_fwd / bqh_mhatt_bwd; q, k, v and the result (B, N, H)"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, hide, keep, heads):
+        from . import _ext
+        qd, kd, vd = q.detach(), k.detach(), v.detach()
+        out, p = _ext.mhatt_fwd(qd, kd, vd, hide, keep, heads)
+        ctx.save_for_backward(qd, kd, vd, p, hide, keep)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import _ext
+        qd, kd, vd, p, hide, keep = ctx.saved_tensors
+        dq, dk, dv = _ext.mhatt_bwd(dout.contiguous(), qd, kd, vd, p, hide, keep, ctx.heads)
+        return dq, dk, dv, None, None, None
 
 
 class FC(nn.Module):
@@ -159,9 +200,32 @@ class MHAtt(nn.Module):
     def _split(self, t, B):
         return t.view(B, -1, self.num_heads, self.head_hidden_size).transpose(1, 2)
 
+    def _fused_ok(self, v, k, q, mask):
+        if not (_FUSED_ATT and _f32_cuda(v, k, q) and q.dim() == 3 and k.dim() == 3 and v.shape == k.shape and q.numel() > 0):
+            return False
+        B, Nq, H = q.shape
+        Nk = k.shape[1]
+        if not (k.shape[0] == B and k.shape[2] == H == self.hidden_size == self.num_heads * self.head_hidden_size
+                and k.device == q.device and v.device == q.device
+                and q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and 0 <= self.dropout.p < 1):
+            return False
+        if mask is not None and not (mask.dtype == torch.bool and mask.is_cuda and mask.device == q.device
+                                     and tuple(mask.shape) == (B, 1, 1, Nk)):
+            return False
+        from . import _ext
+        return _ext.mhatt_ok(H, self.num_heads, Nq, Nk) and B * self.num_heads <= 65535
+
     def forward(self, v, k, q, mask, att_pdrop=0, att_drop_topk=100):
         B = q.size(0)
-        v, k, q = self._split(self.linear_v(v), B), self._split(self.linear_k(k), B), self._split(self.linear_q(q), B)
+        v, k, q = self.linear_v(v), self.linear_k(k), self.linear_q(q)
+        if self._fused_ok(v, k, q, mask):
+            Nq, Nk = q.shape[1], k.shape[1]
+            hide = mask.reshape(B, Nk).contiguous().view(torch.uint8) if mask is not None else None
+            keep = None
+            if self.dropout.training and self.dropout.p > 0:   # the composition's draw: same module, shape, dtype and point
+                keep = self.dropout(torch.ones(B, self.num_heads, Nq, Nk, dtype=torch.float32, device=q.device))
+            return self.linear_merge(_MHAttCoreFn.apply(q, k, v, hide, keep, self.num_heads))
+        v, k, q = self._split(v, B), self._split(k, B), self._split(q, B)
         ctx = self.att(v, k, q, mask, att_pdrop, att_drop_topk)
         return self.linear_merge(ctx.transpose(1, 2).contiguous().view(B, -1, self.hidden_size))
 

@@ -15,6 +15,7 @@
 #include "bqhip_view.h"  /* bq_view_prep: additive to ABI 6 */
 #include "bqhip_beam.h"  /* bqx_beam_step: additive to ABI 6 */
 #include "bqhip_mcan.h"  /* bqm_mcan_ln_* / bqm_attflat_pool_*: additive to ABI 6 */
+#include "bqhip_mhatt.h" /* bqh_mhatt_fwd / bqh_mhatt_bwd: additive to ABI 6 */
 
 #ifdef __cplusplus
 extern "C" {

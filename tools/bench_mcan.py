@@ -1,14 +1,16 @@
 """Times the MCAN blocks with the fused row kernels of csrc/mcan.hip (mcan_module.set_fused(True): residual LayerNorm and AttFlat's
-pooling, one kernel each way) against the torch compositions, same weights, inputs and seed, forward + loss + backward:
+pooling, one kernel each way) against the torch compositions, and as a third route with the attention kernels of csrc/mhatt.hip
+on top of the row kernels (mcan_module.set_fused_attention(True): MHAtt's core, one launch forward and two backward per site),
+same weights, inputs and seed, forward + loss + backward:
 
   * the stage-1 question branch (hotpath.lang_branch_forward: LangModule, MCAN_ED with 2 + 2 layers, two AttFlat heads,
     fusion_norm, the three classifiers) at B in {16, 64} x question length in {14, 32}, 256 proposals, hidden 256;
   * the VQA reference head (hotpath.qa_heads_forward with use_reference: dec_list_qo, 2 SGA layers over 256 proposals against
     the question states) at the same sizes.
 
-HIP events around blocks of calls, warm-up of every shape, the two routes alternated in the same process, the median over the
-blocks; device kernels per call from one call under torch.profiler (a run of its own, after the timing).  The
-profiles/mcan_rows.md table is this tool's output.
+HIP events around blocks of calls, warm-up of every shape, the three routes alternated in the same process, the median over the
+blocks; device kernels per call from one call under torch.profiler (a run of its own, after the timing).  The tables of
+profiles/mcan_rows.md (two routes) and profiles/mhatt.md (three) are this tool's output.
 
     python tools/bench_mcan.py [--blocks 7] [--calls 20] [--warmup 5] [--out OUT.json]
 """
@@ -28,14 +30,15 @@ SIZES = [(16, 14), (16, 32), (64, 14), (64, 32)]      # (B, question length)
 K, HID, EMB, BLIP = 256, 256, 300, 768
 
 
-def with_route(fused, fn):
+def with_route(fused, fn, attention=False):
     def run():
         from bridgeqa_amd import mcan_module
-        prev = mcan_module.set_fused(fused)
+        prev, prev_att = mcan_module.set_fused(fused), mcan_module.set_fused_attention(attention)
         try:
             return fn()
         finally:
             mcan_module.set_fused(prev)
+            mcan_module.set_fused_attention(prev_att)
     return run
 
 
@@ -68,11 +71,12 @@ def _step(module, forward, weights):
     return run
 
 
-def _compare(fn, module, keys):
+def _compare(fn, module, keys, attention=False):
     """largest |difference| of the outputs, and of the parameter gradients relative to the largest gradient entry, between the
-    two routes (one scale for all tensors: the key-projection biases have a gradient of exactly zero in real arithmetic, rounding
-    noise on either route, and would make a per-tensor ratio meaningless)"""
-    out_on = with_route(True, fn)()
+    fused route (with the attention kernels too when `attention`) and the compositions (one scale for all tensors: the
+    key-projection biases have a gradient of exactly zero in real arithmetic, rounding noise on either route, and would make a
+    per-tensor ratio meaningless)"""
+    out_on = with_route(True, fn, attention)()
     g_on = [p.grad.clone() for p in module.parameters() if p.grad is not None]
     out_off = with_route(False, fn)()
     g_off = [p.grad for p in module.parameters() if p.grad is not None]
@@ -109,15 +113,25 @@ def bench(a, dev):
             took = [p - q for p, q in zip(_ext.MCAN_CALLS, c0)]
             want = [11, 11, 2, 2] if name == "branch" else [6, 6, 0, 0]
             assert took == want, "%s: the fused variant launched %s, expected %s" % (name, took, want)
-            t = alternate({"fused": with_route(True, fn), "composition": with_route(False, fn)}, a.warmup, a.blocks, a.calls)
-            row = dict(t, kernels=dict(fused=kernels(with_route(True, fn)), composition=kernels(with_route(False, fn))),
-                       max_abs_diff_out=d_out, max_rel_diff_grad=d_grad)
+            c0, h0 = list(_ext.MCAN_CALLS), list(_ext.MHATT_CALLS)
+            d_out_att, d_grad_att = _compare(fn, module, list(weights), attention=True)
+            assert [p - q for p, q in zip(_ext.MCAN_CALLS, c0)] == want, "%s: the attention route changed the row launches" % name
+            took = [p - q for p, q in zip(_ext.MHATT_CALLS, h0)]
+            want = [6, 6] if name == "branch" else [4, 4]
+            assert took == want, "%s: the attention variant launched %s attention sites, expected %s" % (name, took, want)
+            routes = {"fused": with_route(True, fn), "composition": with_route(False, fn), "fused_att": with_route(True, fn, True)}
+            t = alternate(routes, a.warmup, a.blocks, a.calls)
+            row = dict(t, kernels={k: kernels(r) for k, r in routes.items()}, max_abs_diff_out=d_out, max_rel_diff_grad=d_grad,
+                       max_abs_diff_out_att=d_out_att, max_rel_diff_grad_att=d_grad_att)
             res["%s_B%d_L%d" % (name, B, L)] = row
-            print("%-12s B %2d L %2d  fwd+bwd fused %7.3f ms (min %7.3f max %7.3f)  composition %7.3f ms (min %7.3f max %7.3f) | "
-                  "kernels %d vs %d | max |diff| out %.2g, grads (of the largest) %.2g" % (
+            print("%-12s B %2d L %2d  fwd+bwd fused %7.3f ms (min %7.3f max %7.3f)  composition %7.3f ms (min %7.3f max %7.3f)  "
+                  "fused + attention %7.3f ms (min %7.3f max %7.3f) | kernels %d vs %d vs %d | max |diff| to the composition: "
+                  "out %.2g, grads (of the largest) %.2g; with attention %.2g, %.2g" % (
                       name, B, L, t["fused"]["median_ms"], t["fused"]["min_ms"], t["fused"]["max_ms"],
                       t["composition"]["median_ms"], t["composition"]["min_ms"], t["composition"]["max_ms"],
-                      row["kernels"]["fused"], row["kernels"]["composition"], d_out, d_grad), flush=True)
+                      t["fused_att"]["median_ms"], t["fused_att"]["min_ms"], t["fused_att"]["max_ms"],
+                      row["kernels"]["fused"], row["kernels"]["composition"], row["kernels"]["fused_att"], d_out, d_grad,
+                      d_out_att, d_grad_att), flush=True)
     return res
 
 
